@@ -7,7 +7,7 @@ GaussianAgg(nb_samples=8) (fused native blend with TexturesVertex sampling), L2 
 synthetic target, backward through blend -> rasterizer -> vertices -> pose, Adam step on the
 pose (lr 5e-2, eval.py:337).  The whole step is one captured HIP graph.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|eval]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--config cfg2|cfg3|cfg4|eval] [--full] [--dump-outputs DIR]
     python bench.py --gpus N ...                        (starts N rank processes itself, RCCL)
     torchrun --nproc-per-node N bench.py --gpus N ...   (one rank per GPU, RCCL; --gpus must equal N)
 
@@ -22,8 +22,17 @@ Multi-GPU (--shard):
           120 + 360 r / N: a multi-view pose optimisation step) and one RCCL all-reduce averages
           the pose / smoothing gradients.  value = distinct frames / s.
 
+A plain run sets up, warms up, times the --steps steps and prints the line: `value`, `ms_per_step`
+and what follows from the timed steps alone.  --dump-outputs DIR also writes what the last timed step
+computed (images, loss, gradients, pose after the Adam step) as DIR/<name>.npy, float32.  The inputs
+are seeded, and the pose and Adam's moments are put back to their initial values before that last step
+(Workload.reset_state: the float atomics of the earlier backwards would otherwise leave every run with
+another pose), so two builds run with the same arguments can be compared output for output.  --full adds
+the measurements that take runs of their own after the timed region: the forward / backward split,
+the per-kernel times and roofline, the dense-fragment roofline and the CPU baseline.
+
 Prints ONE JSON line on rank 0: `value` = frames/s (forward + backward per frame) over all
-ranks; `ms_forward` / `ms_backward` = HIP events around separately captured forward and
+ranks; under --full `ms_forward` / `ms_backward` = HIP events around separately captured forward and
 backward(+Adam) graphs replayed right after the timed region; `roofline` is the dominant native
 call's algorithmic HBM bytes / its HIP-event duration; `cpu_baseline` times the CPU oracle
 (test-infrastructure restatement of the reference + PyTorch3D rasterizer) on a bounded sample of
@@ -188,6 +197,34 @@ class Workload:
         self.one = torch.ones((), device=device)
         self.K, self.S, self.Sr, self.H, self.batch = K, samples, Sr, image_size, batch
         self.F = faces.shape[0]
+        # --dump-outputs: the step keeps what it computed (keep()); off, the step holds no extra reference
+        self.keep_outputs = False
+        self.kept = {}
+        self.log_rot0 = self.log_rot.detach().clone()
+
+    def reset_state(self):
+        """The pose and Adam's moments back to their initial values, in place (a captured step keeps its
+        tensors).  The backward's float atomics make two runs' pose trajectories part within a few
+        steps (a pose that differs in the last bit flips perturbed-argmax winners), so --dump-outputs
+        calls this before the last timed step: that step's inputs (pose, optimiser state, the Philox
+        key of its ordinal) are then the same bits in every run, and its outputs compare across
+        builds."""
+        with torch.no_grad():
+            self.log_rot.copy_(self.log_rot0)
+            for st in self.opt.state.values():
+                for v in st.values():
+                    if torch.is_tensor(v):
+                        v.zero_()
+
+    def keep(self, loss):
+        """Hold what a caller of the step receives: the rendered images, the loss and the gradients
+        (detached views, no copies).  A captured step calls this once inside the capture (the tensors
+        are the graph's static outputs, rewritten by every replay), the eager step after every
+        backward."""
+        self.kept.update(loss=loss.detach())
+        for name, p in zip(("grad_log_rot", "grad_sigma", "grad_gamma", "grad_alpha"), self.params()):
+            if p.grad is not None:
+                self.kept[name] = p.grad
 
     def params(self):
         return [self.log_rot, self.rast.sigma, self.agg.gamma, self.agg.alpha]
@@ -202,6 +239,8 @@ class Workload:
         mesh = self.base.update_padded(Rotate(R).transform_points(self.base.verts_padded()))
         kw = {"lights": self.lights} if self.lights is not None else {}
         images = self.renderer(mesh, cameras=self.cameras, **kw)
+        if self.keep_outputs:
+            self.kept["image"] = images.detach()
         if self.loss_kind == "native":
             # eval.py:352-353's ((images[..., :3] - target) ** 2).mean() on the package's fused loss
             # kernels (pose_opt._RgbMse, pr_rgb_mse_*: 2 forward + 1 backward launches, fp32 summation
@@ -372,10 +411,13 @@ def build_step(wl, world, mode, device, grad_weight, dist_on=None):
         wl.opt = torch.optim.Adam([wl.log_rot], lr=5e-2, fused=True)
 
         def step():
-            wl.forward().backward(wl.one)
+            loss = wl.forward()
+            loss.backward(wl.one)
             if dist_on:
                 average_gradients(wl.params(), weight=grad_weight)
             wl.opt.step()
+            if wl.keep_outputs:
+                wl.keep(loss)
             wl.zero_grad()
         return step
 
@@ -398,7 +440,11 @@ def build_step(wl, world, mode, device, grad_weight, dist_on=None):
     # thread_local: CUDA calls of other threads (the RCCL watchdog at N>1) must not void the capture
     with torch.cuda.graph(graph, capture_error_mode="thread_local"):
         ds.advance()
-        wl.forward().backward(wl.one)
+        loss = wl.forward()
+        loss.backward(wl.one)
+        if wl.keep_outputs:
+            wl.keep(loss)
+        del loss
         if not dist_on:
             wl.opt.step()
     wl.graph = graph
@@ -496,6 +542,24 @@ def eager_split(wl, steps):
             float(np.mean([b.elapsed_time(c) for _, b, c in fb])))
 
 
+DUMP_MAX_ELEMS = 4 << 20  # per array: 16 MB of float32, so the seven arrays stay far below 64 MB
+
+
+def fetch_outputs(wl):
+    """What the timed path computed in its last step, on the host: the rendered images, the loss, the
+    gradients of the pose and of the smoothing leaves, and the pose after the Adam step.  float32; an
+    array above DUMP_MAX_ELEMS (the images of cfg4) is a fixed seeded sample of its flattened elements."""
+    torch.cuda.synchronize()
+    out = {}
+    for name, t in dict(wl.kept, log_rot=wl.log_rot.detach()).items():
+        a = np.ascontiguousarray(t.detach().to("cpu", torch.float32).numpy())
+        if a.size > DUMP_MAX_ELEMS:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[idx]
+        out[name] = a
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -512,6 +576,12 @@ def main():
     ap.add_argument("--batch", type=int, default=None, help="meshes per rank")
     ap.add_argument("--loss", choices=["native", "torch"], default="native",
                     help="the step's L2 loss: the package's fused kernels (default) or torch ops")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the forward / backward split, the per-kernel times "
+                         "and roofline, the dense-fragment roofline and the CPU baseline (runs of their own)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed (images, loss, gradients, updated pose) as "
+                         "DIR/<name>.npy (float32, rank 0)")
     ap.add_argument("--cpu-frames", type=int, default=16)
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-dense", action="store_true")
@@ -573,8 +643,12 @@ def main():
         azim = 120.0 + 360.0 * rank / world
         S_local, Sr_local = S, Sr
 
-    mk_wl = lambda: Workload(device, cfg["image_size"], cfg["K"], S_local, seed=0, batch=cfg["batch"], azim=azim,
-                             rast_samples=Sr_local, eval_scene=args.config == "eval", loss=args.loss)
+    def mk_wl():
+        w = Workload(device, cfg["image_size"], cfg["K"], S_local, seed=0, batch=cfg["batch"], azim=azim,
+                     rast_samples=Sr_local, eval_scene=args.config == "eval", loss=args.loss)
+        w.keep_outputs = args.dump_outputs is not None
+        return w
+
     wl = mk_wl()
     P = cfg["batch"] * cfg["image_size"] * cfg["image_size"]
     mode, note = args.mode, None
@@ -594,6 +668,8 @@ def main():
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for i in range(args.steps):
+        if wl.keep_outputs and i == args.steps - 1:
+            wl.reset_state()  # --dump-outputs: a few in-place device writes, no synchronisation
         step()
     torch.cuda.synchronize()
     if dist_on:
@@ -604,6 +680,25 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
 
+    dumped = None
+    if args.dump_outputs is not None and rank == 0:  # before --full's extra passes replay the step again
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        dumped = {}
+        for name, a in fetch_outputs(wl).items():
+            np.save(os.path.join(args.dump_outputs, name + ".npy"), a)
+            dumped[name] = list(a.shape)
+
+    # everything past the headline figure (runs of their own, after the timed region): --full
+    full = kernel_report(args, wl, mode, world, dist_on, P, S_local, headline) if args.full else None
+    result_line(args, cfg, wl, device, mode, note, world, rank, ranks, backend, dist_on, shard, elapsed,
+                S, Sr, S_local, Sr_local, headline, full, dumped)
+    if dist_on:
+        dist.destroy_process_group()
+
+
+def kernel_report(args, wl, mode, world, dist_on, P, S_local, headline):
+    """--full: the forward / backward split, the per-call kernel times of an instrumented eager replica
+    of the step, and the roofline of the dominant kernel: (ms_fwd, ms_bwd, split_from, kern, roof)."""
     n_split = min(args.steps, 20)
     if mode == "graph":
         ms_fwd, ms_bwd = split_fwd_bwd(wl, n_split, world, dist_on)
@@ -682,7 +777,13 @@ def main():
         if tr.get("valu_issue_us"):  # the bound that applies: VALU issue
             roof["valu_issue_us"] = tr["valu_issue_us"]
             roof["valu_frac"] = round(tr["valu_issue_us"] / (1e3 * k_ms), 4)
+    return ms_fwd, ms_bwd, split_from, kern, roof
 
+
+def result_line(args, cfg, wl, device, mode, note, world, rank, ranks, backend, dist_on, shard, elapsed,
+                S, Sr, S_local, Sr_local, headline, full, dumped):
+    """The one JSON line (rank 0).  full: kernel_report()'s tuple under --full, else None: the line then
+    holds the headline figure and what follows from the timed steps alone."""
     B, Hs, K = cfg["batch"], cfg["image_size"], cfg["K"]
     distinct = B * (world if shard == "frames" else 1)  # distinct frames per step
     value = args.steps * distinct / elapsed
@@ -724,9 +825,18 @@ def main():
                    # (tools/launch_blocking_check.py), so eval.py itself runs launches asynchronously here
                    "launch_blocking": {k: os.environ[k] for k in ("HIP_LAUNCH_BLOCKING", "CUDA_LAUNCH_BLOCKING")
                                        if k in os.environ}},
-        "ms_forward": round(ms_fwd, 4), "ms_backward": round(ms_bwd, 4), "fwd_bwd_split_from": split_from,
-        "fwd_frames_per_s": round(distinct * 1e3 / ms_fwd, 2), "kernels": kern, "roofline": roof,
+        "full": full is not None,
     }
+    kern = {}
+    if full is not None:
+        ms_fwd, ms_bwd, split_from, kern, roof = full
+        out.update({"ms_forward": round(ms_fwd, 4), "ms_backward": round(ms_bwd, 4),
+                    "fwd_bwd_split_from": split_from, "fwd_frames_per_s": round(distinct * 1e3 / ms_fwd, 2),
+                    "kernels": kern, "roofline": roof})
+    if dumped is not None:
+        out["outputs"] = {"dir": args.dump_outputs, "arrays": dumped, "dtype": "float32",
+                          "what": "the last timed step, started from the initial pose and Adam state: images, loss, "
+                                  "gradients, pose after the Adam step"}
     # SURVEY §8(d) RNG term: the algorithmic Gaussian draws of the step (the forward's Sr*K rast
     # and Sa*(K+1) agg normals per pixel, regenerated once more by the backward) against the
     # generator's measured peak (tools/philox_bench.hip: Philox4x32-7 + Box-Muller, every lane busy).
@@ -738,7 +848,7 @@ def main():
                   "frac": round(normals * args.steps / elapsed / (RNG_PEAK_NORMALS_PER_S * world), 4),
                   "peak_from": "tools/philox_bench.hip on one MI355X: 690 G Philox4x32-7 blocks/s (the streams' rounds) "
                                "x 4 normals"}
-    if shard == "samples":
+    if shard == "samples" and full is not None:
         # strong scaling: the rasterizer (and the tiny pose kernels) run in full on every rank, the
         # blend on this rank's sample shard; T(N) >= T_rep + T_shard(1) / N bounds the speed-up
         rep_ms = sum(kern[k].get("kernel_ms", kern[k]["ms"]) for k in ("rast_fwd", "rast_bwd") if k in kern)
@@ -750,10 +860,10 @@ def main():
                     f"{S_local} of {S} agg samples)"}
     if note:
         out["note"] = note
-    if rank == 0 and world == 1 and not args.no_dense and args.config != "eval":
+    if full is not None and rank == 0 and world == 1 and not args.no_dense and args.config != "eval":
         # the blend kernels' fraction of HBM peak on dense fragments at this configuration's shape
         out["roofline_dense"] = dense_roofline(device, Hs, K, S, N=B, Sr=Sr)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and headline:
+    if full is not None and rank == 0 and world == 1 and not args.no_cpu_baseline and headline:
         threads, total, model = host_cpus()
         v, dt = cpu_baseline(args.cpu_frames, threads)
         out["cpu_baseline"] = {"value": round(v, 4), "unit": "frames/s (fwd+bwd)", "cores": threads,
@@ -765,8 +875,6 @@ def main():
         out["speedup_vs_cpu"] = round(value / v, 1)
     if rank == 0:
         print(json.dumps(out), flush=True)
-    if dist_on:
-        dist.destroy_process_group()
 
 
 if __name__ == "__main__":

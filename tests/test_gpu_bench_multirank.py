@@ -29,7 +29,7 @@ def test_bench_two_ranks_gloo(shard, extra):
     env = dict(os.environ, PR_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", OMP_NUM_THREADS="2")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "2",
-           "--steps", "3", "--warmup", "2", "--no-cpu-baseline", "--no-dense"] + extra
+           "--steps", "3", "--warmup", "2", "--full", "--no-cpu-baseline", "--no-dense"] + extra
     if shard is not None:
         cmd += ["--shard", shard]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
@@ -53,8 +53,8 @@ def test_bench_gpus_2_spawns_two_ranks_without_a_launcher():
     the ranks the process group saw."""
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     env.update(PR_BENCH_BACKEND="gloo", OMP_NUM_THREADS="2")
-    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "2", "--no-cpu-baseline",
-           "--no-dense", "--image-size", "128"]
+    cmd = [sys.executable, "bench.py", "--gpus", "2", "--steps", "3", "--warmup", "2", "--full",
+           "--no-cpu-baseline", "--no-dense", "--image-size", "128"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -25,7 +25,7 @@ def test_bench_distributed_path_on_one_rccl_rank(mode):
     env = dict(os.environ, PR_BENCH_DIST="1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
            "--master-addr", "127.0.0.1", "--master-port", str(_free_port()), "bench.py", "--gpus", "1",
-           "--steps", "5", "--warmup", "2", "--mode", mode, "--no-cpu-baseline", "--no-dense"]
+           "--steps", "5", "--warmup", "2", "--mode", mode, "--full", "--no-cpu-baseline", "--no-dense"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=240)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -9,7 +9,7 @@ OUT="$R/gpurun_out/ab_$TAG"; mkdir -p "$OUT"
 for i in $(seq 1 "$ROUNDS"); do
   for side in A B; do
     d="$A"; [ "$side" = B ] && d="$B"
-    (cd "$R/$d" && timeout -k 10 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-dense "$@" \
+    (cd "$R/$d" && timeout -k 10 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline --no-dense "$@" \
        > "$OUT/${side}_r$i.json" 2> "$OUT/${side}_r$i.err") || { echo "bench $side r$i failed"; tail -5 "$OUT/${side}_r$i.err"; exit 1; }
     python -c "import json,sys;d=json.load(open(sys.argv[1]));print(sys.argv[2], d['value'], d['ms_per_step'], {k:v['ms'] for k,v in d['kernels'].items()})" "$OUT/${side}_r$i.json" "$side r$i"
     (cd /tmp && export TMPDIR=/tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv \

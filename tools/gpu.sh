@@ -37,7 +37,7 @@ tests() {
 
 bench() {
   local tag="$1"; shift
-  timeout -k 10 600 python bench.py "$@" > "$OUT/bench_$tag.json" 2> "$OUT/bench_$tag.err" || { tail -5 "$OUT/bench_$tag.err"; return 1; }
+  timeout -k 10 600 python bench.py --full "$@" > "$OUT/bench_$tag.json" 2> "$OUT/bench_$tag.err" || { tail -5 "$OUT/bench_$tag.err"; return 1; }
   summ "$OUT/bench_$tag.json" "$tag"
 }
 
@@ -46,7 +46,7 @@ sweep() {
   for spec in "$@"; do
     IFS='|' read -r name envs lib <<< "$spec"
     local libpath=""; [ -n "$lib" ] && libpath="PR_NATIVE_LIB=$R/pertrenderer_amd/$lib.so"
-    env $envs $libpath timeout -k 10 200 python bench.py --config "$cfg" --no-cpu-baseline --no-dense --steps 30 --warmup 5 \
+    env $envs $libpath timeout -k 10 200 python bench.py --full --config "$cfg" --no-cpu-baseline --no-dense --steps 30 --warmup 5 \
       > "$OUT/sw_${tag}_$name.json" 2>> "$OUT/sw_$tag.err" || { echo "FAIL $name"; tail -3 "$OUT/sw_$tag.err"; return 1; }
     summ "$OUT/sw_${tag}_$name.json" "$name"
   done
