@@ -44,7 +44,7 @@
 extern "C" {
 #endif
 
-#define PR_ABI_VERSION 20
+#define PR_ABI_VERSION 21
 
 /* error codes */
 #define PR_OK 0
@@ -192,6 +192,19 @@ typedef struct PRBlendBwdArgs {
   /* grad_vert_colors (VERTEX), grad_light, grad_camera are ACCUMULATED (the caller zeroes them); */
   /* d bary goes to grad_bary (replaces grad_colors)                                            */
 } PRBlendBwdArgs;
+
+/* pr_blend_geometry (ABI 21): the launch geometry pr_blend_fwd / pr_blend_bwd choose for a call */
+typedef struct PRBlendGeometry {
+  int32_t PB;          /* pixels per workgroup */
+  int32_t cap;         /* entry records in LDS */
+  int32_t lds_bytes;   /* dynamic LDS of the launch */
+  int32_t lpp;         /* lanes per pixel in the pixel phases */
+  int32_t multi;       /* cap < PB * (K + 1): the multi-pass kernel */
+  int32_t NC;          /* forward: candidate stripes of the Monte-Carlo argmax (0 for the backward) */
+  int32_t nch;         /* backward: lanes that share an entry's sample sum in B6 (0 for the forward) */
+  int32_t b2_regs;     /* backward: B2 keeps its chunks in registers (else LDS; 0 for the forward) */
+  int32_t interleaved; /* interleaved pixel blocks (else consecutive) */
+} PRBlendGeometry;
 
 typedef struct PRHeavisideArgs {
   int32_t N, H, W, K, Sr, sample_offset_r, noise_mode;
@@ -509,6 +522,10 @@ int pr_blend_fwd(const PRBlendFwdArgs* args, void* stream);
 size_t pr_blend_plan_size(const PRBlendParams* p); /* bytes of PRBlendFwdArgs.plan */
 size_t pr_blend_bwd_workspace_size(const PRBlendBwdArgs* args);
 int pr_blend_bwd(const PRBlendBwdArgs* args, void* stream);
+/* Host only, no launch: the geometry of the static grid (no segment plan) pr_blend_fwd (bwd = 0) or
+ * pr_blend_bwd (bwd != 0) would launch for `p` under the current PR_BLEND_* environment; reads the
+ * shape, sample and flag fields of `p` only (tests assert the path a case takes). */
+int pr_blend_geometry(const PRBlendParams* p, int bwd, PRBlendGeometry* out);
 
 int pr_heaviside_fwd(const PRHeavisideArgs* args, void* stream);
 size_t pr_heaviside_bwd_workspace_size(const PRHeavisideArgs* args);

@@ -65,6 +65,12 @@ class PRBlendBwdArgs(C.Structure):
                 ("pix_count", _vp), ("plan", _vp), ("sync", _vp)]
 
 
+class PRBlendGeometry(C.Structure):
+    _fields_ = [("PB", C.c_int32), ("cap", C.c_int32), ("lds_bytes", C.c_int32), ("lpp", C.c_int32),
+                ("multi", C.c_int32), ("NC", C.c_int32), ("nch", C.c_int32), ("b2_regs", C.c_int32),
+                ("interleaved", C.c_int32)]
+
+
 class PRHeavisideArgs(C.Structure):
     _fields_ = [("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("K", C.c_int32),
                 ("Sr", C.c_int32), ("sample_offset_r", C.c_int32), ("noise_mode", C.c_int32),
@@ -156,6 +162,7 @@ EXPORTS = {
     "pr_blend_fwd": (C.c_int, [C.POINTER(PRBlendFwdArgs), _vp]),
     "pr_blend_bwd_workspace_size": (C.c_size_t, [C.POINTER(PRBlendBwdArgs)]),
     "pr_blend_bwd": (C.c_int, [C.POINTER(PRBlendBwdArgs), _vp]),
+    "pr_blend_geometry": (C.c_int, [C.POINTER(PRBlendParams), C.c_int, C.POINTER(PRBlendGeometry)]),
     "pr_heaviside_fwd": (C.c_int, [C.POINTER(PRHeavisideArgs), _vp]),
     "pr_heaviside_bwd_workspace_size": (C.c_size_t, [C.POINTER(PRHeavisideArgs)]),
     "pr_heaviside_bwd": (C.c_int, [C.POINTER(PRHeavisideArgs), _vp]),
@@ -184,7 +191,7 @@ EXPORTS = {
     "pr_vert_normals_fwd": (C.c_int, [C.POINTER(PRNormalsArgs), _vp]),
     "pr_vert_normals_bwd": (C.c_int, [C.POINTER(PRNormalsArgs), _vp]),
 }
-ABI_VERSION = 20
+ABI_VERSION = 21
 
 _lib = None
 

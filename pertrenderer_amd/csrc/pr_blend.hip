@@ -523,8 +523,26 @@ PR_DEV void tail_pair(uint64_t key, uint32_t gp, uint32_t sg, int m, float& s1, 
 }
 
 PR_DEV int agg_first_group(const PRBlendParams& p) { return p.sample_offset_a >> 2; }
-PR_DEV int agg_num_groups(const PRBlendParams& p) {
+PR_HD int agg_num_groups(const PRBlendParams& p) {
   return ((p.sample_offset_a + p.Sa - 1) >> 2) - (p.sample_offset_a >> 2) + 1;
+}
+
+// Launch-geometry rules shared by the launches, the kernels and pr_blend_geometry (one definition
+// each, so the query reports what runs).
+// Forward, candidate stripes of the Monte-Carlo argmax: slot chunks per (pixel, sample group) so
+// that ~256 threads share the loop, doubled from NC while a stripe keeps at least 4 entries
+PR_HD int fwd_stripes(int NC, int npix, int ng, int KP1) {
+  while (NC < 64 && npix * ng * NC * 2 <= kThreads && (KP1 + NC * 2 - 1) / (NC * 2) >= 4) NC <<= 1;
+  return NC;
+}
+// Backward, B6: lanes that share an entry's sample sum (1 below 8 sample groups, else 2..16)
+PR_HD int b6_lane_split(int ng) {
+  int nch = 1;
+  if (ng >= 8) {
+    nch = 2;
+    while (nch < 16 && 8 * nch <= ng) nch <<= 1;
+  }
+  return nch;
 }
 
 // Kernel arguments: the C ABI block plus, for PR_BLEND_PHONG (colour mode 3), a by-value copy of
@@ -652,8 +670,7 @@ PR_DEV void fwd_tile(const FwdK& a, const Geo& g, const int NC0, const Sc& sc, c
   int lsh = g.lsh, NC = NC0;
   if constexpr (SEG) {
     while (lsh < g.lsh_max && (2 << lsh) * npix <= kThreads) ++lsh;
-    const int ng = agg_num_groups(p);
-    while (NC < 64 && npix * ng * NC * 2 <= kThreads && (KP1 + NC * 2 - 1) / (NC * 2) >= 4) NC <<= 1;
+    NC = fwd_stripes(NC, npix, agg_num_groups(p), KP1);
   }
   const int lpp = 1 << lsh;
   const int64_t pix0 = bpix0 + ps;  // logical: image / plane lookups (blocks keep to one image when interleaved)
@@ -986,6 +1003,9 @@ __global__ void __launch_bounds__(kThreads, PR_BLEND_FWD_WPE) blend_fwd_kernel(F
 #define PR_BLEND_B2R 8
 #endif
 constexpr int kB2R = PR_BLEND_B2R > 0 ? PR_BLEND_B2R : 1;
+// B2's register path: single-pass launches whose per-lane chunk fits kB2R entries (the multi-pass
+// template keeps its VGPR cap); shared with pr_blend_geometry
+PR_HD bool b2_in_regs(bool multi, int KP1, int lpp) { return !multi && KP1 <= kB2R * lpp; }
 // Same entry layout and passes as the forward.  Entries are compacted (a pixel's valid
 // slots + background) when the masked tail is drawn jointly (B6); otherwise every slot
 // keeps its entry, since injected / Cauchy noise needs each masked slot's own d z.
@@ -1204,7 +1224,7 @@ PR_DEV void bwd_tile(const BwdK& a, const Geo& g, const Sc& sc, float* partials,
     // chunks of at most kB2R entries (every pixel of the launch: K + 1 <= kB2R * lpp) are read
     // into registers once; the loops below then touch LDS only for their results (same
     // arithmetic, same order)
-    const bool regs = !MULTI && g.KP1 <= kB2R * lpp;  // (the multi-pass template keeps its VGPR cap)
+    const bool regs = b2_in_regs(MULTI, g.KP1, lpp);
     float rpr[kB2R], rzz[kB2R];
     if (regs) {
 #pragma unroll
@@ -1360,11 +1380,7 @@ PR_DEV void bwd_tile(const BwdK& a, const Geo& g, const Sc& sc, float* partials,
     // the reference divides each sample's a_s * score by gamma (smoothagg.py:52); one
     // reciprocal here instead of an IEEE division per (slot, sample): within 1 ulp
     const float inv_gamma = 1.f / sc.gamma;
-    int nch = 1;
-    if (ng >= 8) {
-      nch = 2;
-      while (nch < 16 && 8 * nch <= ng) nch <<= 1;
-    }
+    const int nch = b6_lane_split(ng);
     const int lch = 31 - __builtin_clz(nch);
     for (int i0 = 0; i0 < nent * nch; i0 += kThreads) {  // uniform trip count (shuffles below)
       const int i = i0 + tid, row = i >> lch, c = i & (nch - 1);
@@ -2089,6 +2105,32 @@ int phong_check(const PRBlendParams& p, const PRShadeArgs* sh) {
 }
 
 
+// The static grid of a call: what pr_blend_fwd / pr_blend_bwd launch and pr_blend_geometry reports
+struct Launch {
+  Geo geo;  // (cap set)
+  size_t lds;
+  bool multi;
+  int NC;  // forward: candidate stripes of the Monte-Carlo argmax
+};
+Launch pick_launch(const PRBlendParams& p, bool bwd) {
+  const int KP1 = p.K + 1;
+  const Shape sh = pick_shape(KP1, p.Sa, (int64_t)p.N * p.H * p.W, bwd);
+  Launch l;
+  l.geo = make_geo(p, sh.PB, bwd);
+  l.geo.cap = sh.cap;
+  l.lds = bwd ? bwd_lds(sh.PB, sh.cap, p.Sa) : fwd_lds(sh.PB, sh.cap);
+  l.multi = sh.cap < sh.PB * KP1;
+  l.NC = bwd ? 0 : fwd_stripes(1, sh.PB, agg_num_groups(p), KP1);
+  return l;
+}
+
+// PR_BLEND_PHONG shades from the mesh, PR_BLEND_VERTEX interpolates vertex colours: color_mode
+// would pick VERTEX silently
+int phong_vertex_check(int flags, const char* msg) {
+  if ((flags & PR_BLEND_PHONG) && (flags & PR_BLEND_VERTEX)) return set_error(PR_ERR_ARG, msg);
+  return PR_OK;
+}
+
 int64_t bwd_blocks(const PRBlendParams& p) {
   const int PB = pick_shape(p.K + 1, p.Sa, (int64_t)p.N * p.H * p.W, true).PB;
   const int64_t P = (int64_t)p.N * p.H * p.W;
@@ -2143,6 +2185,7 @@ extern "C" int pr_blend_fwd(const PRBlendFwdArgs* args, void* stream) {
   const bool rast = a.p.flags & PR_BLEND_RAST, color = a.p.flags & PR_BLEND_COLOR;
   if (int e = check_params(a.p, rast)) return e;
   if (!a.pix_to_face && !a.mask) return set_error(PR_ERR_ARG, "blend_fwd: need pix_to_face or mask");
+  if (int e = phong_vertex_check(a.p.flags, "blend_fwd: PR_BLEND_PHONG and PR_BLEND_VERTEX exclude each other")) return e;
   const int cm = color_mode(a.p.flags);
   if ((a.p.flags & PR_BLEND_WINNERS_IN) && rast)
     return set_error(PR_ERR_ARG, "blend_fwd: PR_BLEND_WINNERS_IN takes probabilities (no PR_BLEND_RAST)");
@@ -2156,19 +2199,14 @@ extern "C" int pr_blend_fwd(const PRBlendFwdArgs* args, void* stream) {
   FwdK k{};
   static_cast<PRBlendFwdArgs&>(k) = a;
   if (cm == 3) k.sh = *a.shade;
-  const int KP1 = a.p.K + 1;
-  const Shape sh = pick_shape(KP1, a.p.Sa, (int64_t)a.p.N * a.p.H * a.p.W, false);
-  const int PB = sh.PB;
-  Geo geo = make_geo(a.p, PB, false);
-  geo.cap = sh.cap;
-  // slot chunks per (pixel, sample group) so that ~256 threads share the MC loop
-  const int ng = ((a.p.sample_offset_a + a.p.Sa - 1) >> 2) - (a.p.sample_offset_a >> 2) + 1;
-  int NC = 1;
-  while (NC < 64 && PB * ng * NC * 2 <= kThreads && (KP1 + NC * 2 - 1) / (NC * 2) >= 4) NC <<= 1;
+  const Launch ln = pick_launch(a.p, false);
+  Geo geo = ln.geo;
+  const int PB = geo.PB;
+  const int NC = ln.NC;
   int64_t nblk = (geo.P + PB - 1) / PB;
-  const size_t lds = fwd_lds(PB, sh.cap);
+  const size_t lds = ln.lds;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  const bool multi = sh.cap < PB * KP1;
+  const bool multi = ln.multi;
   const PlanCfg pc = a.plan ? plan_cfg(a.p, a.pix_count) : PlanCfg{};
   if (pc.on) {  // entry-balanced segments (blend_plan_kernel) taken by resident workgroups
     blend_plan_count_kernel<<<(pc.q.P + kThreads - 1) / kThreads, kThreads, 0, st>>>(a.pix_count, pc.q, a.plan);
@@ -2190,6 +2228,24 @@ extern "C" int pr_blend_fwd(const PRBlendFwdArgs* args, void* stream) {
   return check_launch("blend_fwd");
 }
 
+
+extern "C" int pr_blend_geometry(const PRBlendParams* p, int bwd, PRBlendGeometry* out) {
+  if (!p || !out) return set_error(PR_ERR_ARG, "blend_geometry: null args");
+  if (p->flags & PR_BLEND_SOFT) return set_error(PR_ERR_ARG, "blend_geometry: PR_BLEND_SOFT has its own geometry");
+  if (p->N <= 0 || p->H <= 0 || p->W <= 0 || p->K <= 0 || p->K > 255 || p->Sa <= 0 || p->Sa > 4096)
+    return set_error(PR_ERR_ARG, "blend_geometry: bad shape");
+  const Launch ln = pick_launch(*p, bwd != 0);
+  out->PB = ln.geo.PB;
+  out->cap = ln.geo.cap;
+  out->lds_bytes = (int32_t)ln.lds;
+  out->lpp = ln.geo.lpp;
+  out->multi = ln.multi;
+  out->NC = ln.NC;
+  out->nch = bwd ? b6_lane_split(agg_num_groups(*p)) : 0;
+  out->b2_regs = bwd ? b2_in_regs(ln.multi, ln.geo.KP1, ln.geo.lpp) : 0;
+  out->interleaved = ln.geo.pm;
+  return PR_OK;
+}
 
 extern "C" size_t pr_blend_plan_size(const PRBlendParams* p) {
   if (!p || (p->flags & PR_BLEND_SOFT)) return 0;
@@ -2215,6 +2271,7 @@ extern "C" int pr_blend_bwd(const PRBlendBwdArgs* args, void* stream) {
   const bool rast = a.p.flags & PR_BLEND_RAST, color = a.p.flags & PR_BLEND_COLOR;
   if (int e = check_params(a.p, rast)) return e;
   if (!a.pix_to_face && !a.mask) return set_error(PR_ERR_ARG, "blend_bwd: need pix_to_face or mask");
+  if (int e = phong_vertex_check(a.p.flags, "blend_bwd: PR_BLEND_PHONG and PR_BLEND_VERTEX exclude each other")) return e;
   if (!a.zbuf || !a.winners || !a.grad_zbuf || !a.grad_scalars ||
       (rast && (!a.dists || !a.grad_dists)) || (!rast && (!a.prob || !a.grad_prob)) ||
       (color_mode(a.p.flags) == 1 && (!a.colors || !a.grad_image || !a.grad_colors)) ||
@@ -2232,16 +2289,14 @@ extern "C" int pr_blend_bwd(const PRBlendBwdArgs* args, void* stream) {
   BwdK k{};
   static_cast<PRBlendBwdArgs&>(k) = a;
 
-  const int KP1 = a.p.K + 1;
-  const Shape sh = pick_shape(KP1, a.p.Sa, (int64_t)a.p.N * a.p.H * a.p.W, true);
-  const int PB = sh.PB;
-  Geo geo = make_geo(a.p, PB, true);
-  geo.cap = sh.cap;
+  const Launch ln = pick_launch(a.p, true);
+  Geo geo = ln.geo;
+  const int PB = geo.PB;
   int64_t nblk = (geo.P + PB - 1) / PB;
-  size_t lds = bwd_lds(PB, sh.cap, a.p.Sa);
+  const size_t lds = ln.lds;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   float* part = reinterpret_cast<float*>(a.workspace);
-  const bool multi = sh.cap < PB * KP1;
+  const bool multi = ln.multi;
   const PlanCfg pc = a.plan ? plan_cfg(a.p, a.pix_count) : PlanCfg{};
   if (pc.on) {  // the forward's plan: entry-balanced segments taken by resident workgroups
     geo.lsh_max = pc.lsh_max[1];

@@ -30,8 +30,46 @@ def test_library_exports_every_declared_symbol():
 
 def test_abi_version_and_error_string():
     lib = nat.load()
-    assert lib.pr_abi_version() == nat.ABI_VERSION
+    assert lib.pr_abi_version() == nat.ABI_VERSION == 21
     assert isinstance(lib.pr_last_error(), bytes)
+
+
+def _blend_params(N, H, W, K, Sa, flags=0):
+    p = nat.PRBlendParams()
+    p.N, p.H, p.W, p.K, p.Sr, p.Sa, p.flags = N, H, W, K, 4, Sa, flags
+    return p
+
+
+def test_blend_geometry_query(monkeypatch):
+    """pr_blend_geometry (host only) reports the launch pr_blend_fwd / pr_blend_bwd would make:
+    pick_shape's block and capacity, make_geo's lanes per pixel, the forward's stripes, the
+    backward's B2 path and B6 lane split."""
+    for k in ("PR_BLEND_PB_FWD", "PR_BLEND_PB_BWD", "PR_BLEND_LDS_KB_FWD", "PR_BLEND_LDS_KB_BWD", "PR_BLEND_INTERLEAVE"):
+        monkeypatch.delenv(k, raising=False)
+    lib = nat.load()
+    g = nat.PRBlendGeometry()
+    # a small frame: 32-pixel forward blocks, 16-pixel backward blocks, one pass, registers in B2
+    p = _blend_params(1, 8, 8, 12, 4)
+    assert lib.pr_blend_geometry(p, 0, g) == 0
+    assert (g.PB, g.cap, g.lpp, g.multi, g.NC, g.nch, g.b2_regs, g.interleaved) == (32, 32 * 13, 8, 0, 4, 0, 0, 0)
+    assert g.lds_bytes == (2 * g.cap + 9 * g.PB + 7) * 4 + 3 * g.cap
+    assert lib.pr_blend_geometry(p, 1, g) == 0
+    assert (g.PB, g.cap, g.lpp, g.multi, g.NC, g.nch, g.b2_regs, g.interleaved) == (16, 16 * 13, 8, 0, 0, 1, 1, 0)
+    assert g.lds_bytes == (6 * g.cap + g.PB * 4 + 17 * g.PB + 3) * 4 + g.cap + g.PB * 4
+    # a cfg 4 frame (16 x 512^2, K = 150, Sa = 64): 32-pixel multi-pass interleaved backward, 4-lane B6
+    p = _blend_params(16, 512, 512, 150, 64)
+    assert lib.pr_blend_geometry(p, 1, g) == 0
+    assert (g.PB, g.lpp, g.multi, g.nch, g.b2_regs, g.interleaved) == (32, 8, 1, 4, 0, 1)
+    assert g.cap < g.PB * 151 and g.lds_bytes <= 24 * 1024
+    # the environment is read per call
+    monkeypatch.setenv("PR_BLEND_PB_BWD", "4")
+    assert lib.pr_blend_geometry(_blend_params(1, 6, 6, 150, 8), 1, g) == 0
+    assert (g.PB, g.lpp, g.multi, g.b2_regs) == (4, 32, 0, 1)
+    # bad arguments
+    assert lib.pr_blend_geometry(None, 0, g) == -1 and lib.pr_blend_geometry(p, 0, None) == -1
+    assert lib.pr_blend_geometry(_blend_params(1, 8, 8, 0, 4), 0, g) == -1
+    assert b"blend_geometry" in lib.pr_last_error()
+    assert lib.pr_blend_geometry(_blend_params(1, 8, 8, 12, 4, nat.PR_BLEND_SOFT), 0, g) == -1
 
 
 def test_argument_validation_without_gpu():
@@ -40,6 +78,14 @@ def test_argument_validation_without_gpu():
     a = nat.PRBlendFwdArgs()  # all zero: empty shape
     assert lib.pr_blend_fwd(a, None) == -1
     assert b"empty shape" in lib.pr_last_error()
+    # PR_BLEND_PHONG | PR_BLEND_VERTEX: rejected before the colour mode is chosen (VERTEX would win)
+    buf = C.create_string_buffer(64)  # stands in for every required pointer: rejected before any is read
+    flags = nat.PR_BLEND_RAST | nat.PR_BLEND_COLOR | nat.PR_BLEND_PHONG | nat.PR_BLEND_VERTEX
+    for args, fn in ((nat.PRBlendFwdArgs(), lib.pr_blend_fwd), (nat.PRBlendBwdArgs(), lib.pr_blend_bwd)):
+        args.p = _blend_params(1, 2, 2, 3, 4, flags)
+        args.p.znear = args.p.zfar = args.pix_to_face = C.addressof(buf)
+        assert fn(args, None) == -1
+        assert b"PR_BLEND_PHONG and PR_BLEND_VERTEX exclude each other" in lib.pr_last_error()
     r = nat.PRRastArgs()
     assert lib.pr_rast_fwd(r, None) == -1
     assert lib.pr_pose_step(nat.PRPoseStepArgs(), None) == -1
