@@ -151,6 +151,43 @@ PR_DEV void write_face_rec(const float v[9], float blur, int cull_backfaces, Fac
   *bbox = pack_box(xmin, xmax, ymin, ymax);
 }
 
+// ---- chunk boxes: the union of the packed cull boxes of each chunk of kChunk consecutive packed
+//      faces, the first level of the tiles' two-level cull (a tile tests a chunk's box before it
+//      loads the chunk's face boxes).  It takes the place of the chunk's first face's box in the
+//      box array (the workspace does not grow); that one face is culled by the exact box of its
+//      record instead (exact_box: a subset of its fp16 box, and what the per-pixel test checks
+//      anyway).  The union is taken over the fp16 boxes the tiles test, so a chunk box contains
+//      every box of its faces; culled faces (+inf / -inf) drop out of fminf / fmaxf, and a chunk
+//      of culled faces keeps the empty box every tile rejects.  A box with a NaN bound passes the
+//      tile test (every comparison is false), so a chunk that holds one gets the all-covering box
+//      and is never rejected.  Chunks count over the packed face index: one that straddles two
+//      meshes is only less tight.  (32-face chunks measured equal)
+constexpr int kChunk = 64;  // one wave's lanes
+
+// Called by every lane of a wave whose lanes hold the faces f - lane .. f - lane + 63 (f - lane a
+// multiple of 64), after the faces' own boxes are written; `live` is false past the last face.
+PR_DEV void write_chunk_box(uint2 packed, bool live, int64_t f, uint2* bbox) {
+  const float inf = __builtin_inff();
+  float4 bb = live ? unpack_box(packed) : make_float4(inf, -inf, inf, -inf);
+  const bool nan = __ballot(bb.x != bb.x || bb.y != bb.y || bb.z != bb.z || bb.w != bb.w) != 0;
+#pragma unroll
+  for (int o = 1; o < kChunk; o <<= 1) {
+    bb.x = fminf(bb.x, __shfl_xor(bb.x, o));
+    bb.y = fmaxf(bb.y, __shfl_xor(bb.y, o));
+    bb.z = fminf(bb.z, __shfl_xor(bb.z, o));
+    bb.w = fmaxf(bb.w, __shfl_xor(bb.w, o));
+  }
+  if (live && (__lane_id() & 63u) == 0)
+    bbox[f] = nan ? pack_box(-inf, inf, -inf, inf) : pack_box(bb.x, bb.y, bb.z, bb.w);
+}
+
+// the exact blur-grown box of a face record (xmin, xmax, ymin, ymax): the cull box of a chunk's
+// first face, whose slot in the box array holds the chunk box
+PR_DEV float4 exact_box(const FaceRec* r) {
+  const float4 c = r->c, d = r->d;
+  return make_float4(c.y, c.z, c.w, d.x);
+}
+
 // ---- coarse bins (PyTorch3D's bin_size / max_faces_per_bin, rasterize_meshes.py): bins of
 //      bs x bs pixels (bs a multiple of every tile shape), per mesh.  The face pass appends
 //      each face to the bins its blur-grown box overlaps (an atomic per (face, bin)); a tile
@@ -234,12 +271,21 @@ PR_DEV int mesh_of_sorted(const int64_t* first, int N, int64_t f) {
 __global__ void face_prep_kernel(const float* fv, int64_t F, float blur_v, const float* blur_dev, int cull_backfaces,
                                  FaceRec* out, uint2* bbox, BinGrid bins, const int64_t* mesh_first, int N) {
   const float blur = blur_dev ? *blur_dev : blur_v;
-  for (int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; f < F; f += (int64_t)gridDim.x * blockDim.x) {
-    float v[9];
+  // whole waves iterate (a wave's 64 lanes hold 64 consecutive faces: the chunk boxes' reduction)
+  for (int64_t f0 = (int64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); f0 < F;
+       f0 += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t f = f0 + (threadIdx.x & 63u);
+    const bool live = f < F;
+    uint2 packed = make_uint2(0u, 0u);
+    if (live) {
+      float v[9];
 #pragma unroll
-    for (int i = 0; i < 9; ++i) v[i] = fv[f * 9 + i];
-    write_face_rec(v, blur, cull_backfaces, out + f, bbox + f);
-    if (bins.count) bin_face(bins, mesh_of_sorted(mesh_first, N, f), f, bbox[f]);
+      for (int i = 0; i < 9; ++i) v[i] = fv[f * 9 + i];
+      write_face_rec(v, blur, cull_backfaces, out + f, bbox + f);
+      packed = bbox[f];
+      if (bins.count) bin_face(bins, mesh_of_sorted(mesh_first, N, f), f, packed);
+    }
+    write_chunk_box(packed, live, f, bbox);
   }
 }
 
@@ -448,6 +494,10 @@ template <int SL> constexpr int rast_qpad() { return PR_RAST_QPAD; }
 #define PR_RAST_CULLU 16
 #endif
 constexpr int kCullU = PR_RAST_CULLU;  // 64-face cull chunks whose boxes are in flight together
+#ifndef PR_RAST_CHUNKU  // the same for the two-level cull's passes over surviving chunks (a sphere_642
+#define PR_RAST_CHUNKU 16  // tile keeps up to 17 of its 20 chunks; further ones take another group)
+#endif
+constexpr int kChunkU = PR_RAST_CHUNKU;
 
 // Bitonic sort (ascending key) of n2 (power of two) LDS entries by NT threads.
 template <int NT>
@@ -583,6 +633,12 @@ PR_DEV int quad_rot(int v, int r) {
   }
 }
 
+// v, which the caller knows to be the same in every lane, as a scalar
+PR_DEV int64_t uniform64(int64_t v) {
+  return (int64_t)(((uint64_t)(uint32_t)__builtin_amdgcn_readfirstlane((int)(v >> 32)) << 32) |
+                   (uint32_t)__builtin_amdgcn_readfirstlane((int)v));
+}
+
 // Forward: per-pixel K nearest (z, face) keys -> pix_to_face, zbuf (+ barycentrics and
 // signed distances with FRAG).  One wave per tile of TP = 64 / SL pixels (8x8, 8x4 or
 // 4x4); lane = pixel * SL + slice.  The SL lanes of a pixel (one DPP quad) split the
@@ -591,10 +647,12 @@ PR_DEV int quad_rot(int v, int r) {
 // in turn, the pixel's queue state (size, last key) travelling between them by DPP.
 // Slicing cuts the heaviest tiles' serial face loop (the kernel's critical path) by SL
 // while the per-pixel queue keeps LDS at K*TP*8 B, so several tiles share a SIMD.
-// Per round: cull the mesh's faces against the tile (boxes of 16 chunks in flight,
-// ballot compaction), sort the survivors by their depth near the tile centre, then
-// walk the sorted list in CH-face chunks staged in LDS, each lane testing kGroup faces
-// at once (independent chains).  The queue is an LDS column sorted by (z, face id),
+// Per round: cull the mesh's faces against the tile (first the union boxes of 64-face
+// chunks, then the face boxes of the chunks that survive, 16 chunks in flight, ballot
+// compaction; PR_RAST_CHUNK_CULL=0 or a bin list: every face box), sort the survivors by
+// their depth near the tile centre, then walk the sorted list in CH-face chunks staged in
+// LDS, each lane testing kGroup faces at once (independent chains).  The queue is an LDS
+// column sorted by (z, face id),
 // PyTorch3D's order, and ends as the K smallest keys of all candidates: it depends
 // neither on SL nor on the traversal order.
 //
@@ -627,8 +685,8 @@ PR_DEV void ring_tile(int b, int m, int& tx, int& ty) {
 // one-wave kernel's: the same fragments bit for bit.
 template <int SL, bool PERSP, bool CLIP, bool FRAG, int NW>
 __global__ void __launch_bounds__(64 * NW, NW == 2 ? PR_RAST_DUO_WPE : PR_RAST_WPE)
-    rast_fwd_kernel(PRRastArgs a, const FaceRec* __restrict__ faces, const uint2* __restrict__ fbox, int ring,
-                    BinGrid bins) {
+    rast_fwd_kernel(PRRastArgs a, const FaceRec* __restrict__ faces, const uint2* __restrict__ fbox,
+                    int chunk_cull, int ring, BinGrid bins) {
   constexpr int TW = SL >= 4 ? 4 : 8, TH = 64 / SL / TW, TP = TW * TH;
   constexpr int kCap = RastCfg<SL>::CAP, kGroup = RastCfg<SL>::G, CH = RastCfg<SL>::CH;
   constexpr int QS = TP + rast_qpad<SL>();  // queue row stride (entries): padding spreads a pixel's rows over banks
@@ -652,6 +710,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 2 ? PR_RAST_DUO_WPE : PR_RAST_W
   float* lsuf = lkey;                                               //   suffix min of z_min
   int* lidx = reinterpret_cast<int*>(lkey + kCap);                  // [kCap] sorted -> cull order
   int64_t* lctl = reinterpret_cast<int64_t*>(lidx + kCap);          // [2] round: next cull position, list size
+  int* lscr = reinterpret_cast<int*>(lctl);  // scratch word of wave 0's cull: lctl is written after the cull only
   const int n = blockIdx.z;
   const int H = a.H, W = a.W;
   int tile_x = blockIdx.x, tile_y = blockIdx.y;
@@ -700,6 +759,85 @@ __global__ void __launch_bounds__(64 * NW, NW == 2 ? PR_RAST_DUO_WPE : PR_RAST_W
     //      chunks' boxes in flight at once, appended in face order without atomics; a
     //      chunk that would overflow the round's list starts the next round (wave 0)
     int nl = 0;
+    // Two-level cull (no bin list): the boxes of up to 64 chunks first, one per lane (each in its
+    // first face's slot of the box array), then the face boxes of the surviving chunks only,
+    // kChunkU chunks in flight together.  A chunk's first face (lane 0 of its pass) is tested
+    // against its record's exact box, fetched by lane u for pass u.  `base` stays 0 or at a
+    // chunk's first face, and jumps over rejected chunks.  The faces listed are a superset of the
+    // faces whose exact box meets the tile and a subset of those whose fp16 box does, like the flat
+    // scan's; chunk_cull = 0 rejects no chunk, which is the flat scan.
+    // The loop runs on scalar copies of the wave-uniform state (the compiler cannot see that the
+    // tile, and so the face range, is the same in every lane), so its chunk picking is scalar code.
+    if (__builtin_amdgcn_readfirstlane(ids == nullptr && wv == 0)) {
+      const int64_t ufb = uniform64(fb), ufe = uniform64(fe);
+      const int f_lo = (int)ufb, f_hi = (int)(ufb + ufe);  // packed face indices fit an int (rast_check)
+      const int cN = (int)((ufb + ufe - 1) / kChunk) + 1;
+      int64_t ub = uniform64(base);
+      int un = 0;
+      while (ub < ufe && un <= kCap - 64) {
+        const int c0 = (int)((ufb + ub) / kChunk);  // this window's chunks: [c0, min(c0 + 64, cN))
+        bool ck = c0 + lane < cN;
+        if (ck && chunk_cull) {
+          const float4 cb = unpack_box(fbox[(c0 + lane) * kChunk]);
+          ck = !(cb.x > txmax || cb.y < txmin || cb.z > tymax || cb.w < tymin);
+        }
+        uint64_t live = __ballot(ck);
+        const int64_t wend = (int64_t)(c0 + 64 < cN ? c0 + 64 : cN) * kChunk - ufb;  // the window's end
+        int64_t next = wend;  // where the cull goes on: the first chunk not yet listed
+        while (live != 0 && un <= kCap - 64) {
+          uint2 pb[kChunkU];
+          const uint64_t live0 = live;
+          const int nlive = __popcll(live);
+          const int np = nlive < kChunkU ? nlive : kChunkU;  // passes of this group, one chunk each
+          int g = -1;  // lane u: the first face of pass u's chunk
+#pragma unroll
+          for (int u = 0; u < kChunkU; ++u) {
+            pb[u] = make_uint2(0u, 0u);  // (defined on every path: no register held across the round)
+            if (u < np) {
+              const int f0 = (c0 + __builtin_ctzll(live)) * kChunk, f = f0 + lane;
+              live &= live - 1;
+              pb[u] = fbox[f >= f_lo && f < f_hi ? f : f_lo];
+              if (lane == u) g = f0;
+            }
+          }
+          float4 ex = make_float4(0.f, 0.f, 0.f, 0.f);
+          if (g >= f_lo && g < f_hi) ex = exact_box(faces + g);
+          uint64_t lv = live0;
+          int stop = -1;  // the pass that would overflow the list: it starts the next round
+#pragma unroll
+          for (int u = 0; u < kChunkU; ++u) {
+            if (u < np && stop < 0) {
+              const uint64_t lv0 = lv;
+              const int f = (c0 + __builtin_ctzll(lv)) * kChunk + lane;
+              lv &= lv - 1;
+              float4 bb = unpack_box(pb[u]);
+              const float e0 = __shfl(ex.x, u), e1 = __shfl(ex.y, u), e2 = __shfl(ex.z, u), e3 = __shfl(ex.w, u);
+              if (lane == 0) bb = make_float4(e0, e1, e2, e3);
+              const bool keep = f >= f_lo && f < f_hi && !(bb.x > txmax || bb.y < txmin || bb.z > tymax || bb.w < tymin);
+              const uint64_t bal = __ballot(keep);
+              const int cnt = __popcll(bal);
+              if (un + cnt > kCap) {
+                stop = u;
+                live = lv0;  // back to the stopped pass's chunk
+              } else {
+                // no branch on keep (under one the compiler takes this loop's scalar state for
+                // per-lane values): the other lanes write the scratch word
+                *(keep ? lfid + un + __popcll(bal & ((1ull << lane) - 1ull)) : lscr) = f;
+                un += cnt;
+              }
+            }
+          }
+          // (set after every group: a chunk listed by this group must not be visited again)
+          next = live != 0 ? (int64_t)(c0 + __builtin_ctzll(live)) * kChunk - ufb : wend;
+          if (stop >= 0) live = 0;
+        }
+        next = next > ub ? next : ub;  // (a stopped pass is never a group's first: ub moves on)
+        ub = next < ufe ? next : ufe;
+      }
+      base = ub;
+      nl = un;
+    }
+    // a bin's list (ids): the flat scan over its faces
     while (wv == 0 && base < fe && nl <= kCap - 64) {
       uint2 pb[kCullU];  // packed fp16 boxes: half the registers of unpacked ones
       int fi[kCullU];
@@ -716,7 +854,8 @@ __global__ void __launch_bounds__(64 * NW, NW == 2 ? PR_RAST_DUO_WPE : PR_RAST_W
 #pragma unroll
       for (int u = 0; u < kCullU; ++u) {
         const int64_t i = base + u * 64 + lane;
-        const float4 bb = unpack_box(pb[u]);
+        float4 bb = unpack_box(pb[u]);
+        if ((fi[u] & (kChunk - 1)) == 0) bb = exact_box(faces + fi[u]);  // its slot holds the chunk box
         const bool keep = i < fe && !(bb.x > txmax || bb.y < txmin || bb.z > tymax || bb.w < tymin);
         const uint64_t bal = __ballot(keep);
         const int cnt = __popcll(bal);
@@ -1230,7 +1369,7 @@ __global__ void __launch_bounds__(64 * NW, NW == 2 ? PR_RAST_DUO_WPE : PR_RAST_W
 }
 
 template <int SL, bool PERSP, bool CLIP>
-void launch_rast_fwd_sl(const PRRastArgs& a, const FaceRec* fr, const uint2* fb, bool frag, size_t lds,
+void launch_rast_fwd_sl(const PRRastArgs& a, const FaceRec* fr, const uint2* fb, int cc, bool frag, size_t lds,
                         const BinGrid& bins, hipStream_t st, int nw) {
   constexpr int TW = SL >= 4 ? 4 : 8, TH = 64 / SL / TW;
   dim3 grid((a.W + TW - 1) / TW, (a.H + TH - 1) / TH, a.N);
@@ -1244,33 +1383,33 @@ void launch_rast_fwd_sl(const PRRastArgs& a, const FaceRec* fr, const uint2* fb,
   ktimer_mark(0, "rast_fwd_kernel", st);
   if constexpr (SL == 4) {
     if (nw == 2) {
-      if (frag) rast_fwd_kernel<SL, PERSP, CLIP, true, 2><<<grid, 128, lds, st>>>(a, fr, fb, ring, bins);
-      else rast_fwd_kernel<SL, PERSP, CLIP, false, 2><<<grid, 128, lds, st>>>(a, fr, fb, ring, bins);
+      if (frag) rast_fwd_kernel<SL, PERSP, CLIP, true, 2><<<grid, 128, lds, st>>>(a, fr, fb, cc, ring, bins);
+      else rast_fwd_kernel<SL, PERSP, CLIP, false, 2><<<grid, 128, lds, st>>>(a, fr, fb, cc, ring, bins);
       ktimer_mark(1, "rast_fwd_kernel", st);
       return;
     }
   }
-  if (frag) rast_fwd_kernel<SL, PERSP, CLIP, true, 1><<<grid, 64, lds, st>>>(a, fr, fb, ring, bins);
-  else rast_fwd_kernel<SL, PERSP, CLIP, false, 1><<<grid, 64, lds, st>>>(a, fr, fb, ring, bins);
+  if (frag) rast_fwd_kernel<SL, PERSP, CLIP, true, 1><<<grid, 64, lds, st>>>(a, fr, fb, cc, ring, bins);
+  else rast_fwd_kernel<SL, PERSP, CLIP, false, 1><<<grid, 64, lds, st>>>(a, fr, fb, cc, ring, bins);
   ktimer_mark(1, "rast_fwd_kernel", st);
 }
 
 template <bool PERSP, bool CLIP>
-void launch_rast_fwd_pc(const PRRastArgs& a, const FaceRec* fr, const uint2* fb, int sl, bool frag, size_t lds,
-                        const BinGrid& bins, hipStream_t st, int nw) {
-  if (sl == 8) launch_rast_fwd_sl<8, PERSP, CLIP>(a, fr, fb, frag, lds, bins, st, 1);
-  else if (sl == 4) launch_rast_fwd_sl<4, PERSP, CLIP>(a, fr, fb, frag, lds, bins, st, nw);
-  else if (sl == 2) launch_rast_fwd_sl<2, PERSP, CLIP>(a, fr, fb, frag, lds, bins, st, 1);
-  else launch_rast_fwd_sl<1, PERSP, CLIP>(a, fr, fb, frag, lds, bins, st, 1);
+void launch_rast_fwd_pc(const PRRastArgs& a, const FaceRec* fr, const uint2* fb, int cc, int sl, bool frag,
+                        size_t lds, const BinGrid& bins, hipStream_t st, int nw) {
+  if (sl == 8) launch_rast_fwd_sl<8, PERSP, CLIP>(a, fr, fb, cc, frag, lds, bins, st, 1);
+  else if (sl == 4) launch_rast_fwd_sl<4, PERSP, CLIP>(a, fr, fb, cc, frag, lds, bins, st, nw);
+  else if (sl == 2) launch_rast_fwd_sl<2, PERSP, CLIP>(a, fr, fb, cc, frag, lds, bins, st, 1);
+  else launch_rast_fwd_sl<1, PERSP, CLIP>(a, fr, fb, cc, frag, lds, bins, st, 1);
 }
 
-void launch_rast_fwd(const PRRastArgs& a, const FaceRec* fr, const uint2* fb, int sl, bool frag, size_t lds,
-                     const BinGrid& bins, hipStream_t st, int nw) {
+void launch_rast_fwd(const PRRastArgs& a, const FaceRec* fr, const uint2* fb, int cc, int sl, bool frag,
+                     size_t lds, const BinGrid& bins, hipStream_t st, int nw) {
   const bool persp = a.perspective_correct != 0, clip = a.clip_barycentric_coords != 0;
-  if (persp && clip) launch_rast_fwd_pc<true, true>(a, fr, fb, sl, frag, lds, bins, st, nw);
-  else if (persp) launch_rast_fwd_pc<true, false>(a, fr, fb, sl, frag, lds, bins, st, nw);
-  else if (clip) launch_rast_fwd_pc<false, true>(a, fr, fb, sl, frag, lds, bins, st, nw);
-  else launch_rast_fwd_pc<false, false>(a, fr, fb, sl, frag, lds, bins, st, nw);
+  if (persp && clip) launch_rast_fwd_pc<true, true>(a, fr, fb, cc, sl, frag, lds, bins, st, nw);
+  else if (persp) launch_rast_fwd_pc<true, false>(a, fr, fb, cc, sl, frag, lds, bins, st, nw);
+  else if (clip) launch_rast_fwd_pc<false, true>(a, fr, fb, cc, sl, frag, lds, bins, st, nw);
+  else launch_rast_fwd_pc<false, false>(a, fr, fb, cc, sl, frag, lds, bins, st, nw);
 }
 
 // Forward, pass 2: barycentrics (perspective-corrected, clipped) and signed squared
@@ -1813,24 +1952,32 @@ __global__ void project_prep_kernel(PRProjectArgs a, float blur_v, const float* 
     for (int k = 0; k < a.seed_advance_n; ++k) s = seed_next(s);
     a.seed_advance[i] = s;
   }
-  for (int64_t f = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; f < a.F; f += stride) {
-    const int n = mesh_of(a.mesh_first_face, a.mesh_num_faces, a.N, f);
-    float fv[9];
+  // whole waves iterate (a wave's 64 lanes hold 64 consecutive faces: the chunk boxes' reduction)
+  for (int64_t f0 = (int64_t)blockIdx.x * blockDim.x + (threadIdx.x & ~63u); f0 < a.F; f0 += stride) {
+    const int64_t f = f0 + (threadIdx.x & 63u);
+    const bool live = f < a.F;
+    uint2 packed = make_uint2(0u, 0u);
+    if (live) {
+      const int n = mesh_of(a.mesh_first_face, a.mesh_num_faces, a.N, f);
+      float fv[9];
 #pragma unroll
-    for (int i = 0; i < 3; ++i) {
-      const float* v = a.verts + a.faces[f * 3 + i] * 3;
-      float o[4], c[4];
-      xform(a.world_to_view + n * 16, v[0], v[1], v[2], o);
-      const float vx = o[0] / o[3], vy = o[1] / o[3], vz = o[2] / o[3];
-      xform(a.proj + n * 16, vx, vy, vz, c);
-      fv[i * 3 + 0] = c[0] / c[3];
-      fv[i * 3 + 1] = c[1] / c[3];
-      fv[i * 3 + 2] = vz;
+      for (int i = 0; i < 3; ++i) {
+        const float* v = a.verts + a.faces[f * 3 + i] * 3;
+        float o[4], c[4];
+        xform(a.world_to_view + n * 16, v[0], v[1], v[2], o);
+        const float vx = o[0] / o[3], vy = o[1] / o[3], vz = o[2] / o[3];
+        xform(a.proj + n * 16, vx, vy, vz, c);
+        fv[i * 3 + 0] = c[0] / c[3];
+        fv[i * 3 + 1] = c[1] / c[3];
+        fv[i * 3 + 2] = vz;
+      }
+#pragma unroll
+      for (int i = 0; i < 9; ++i) a.face_verts[f * 9 + i] = fv[i];
+      write_face_rec(fv, blur, cull_backfaces, recs + f, bbox + f);
+      packed = bbox[f];
+      if (bins.count) bin_face(bins, n, f, packed);
     }
-#pragma unroll
-    for (int i = 0; i < 9; ++i) a.face_verts[f * 9 + i] = fv[i];
-    write_face_rec(fv, blur, cull_backfaces, recs + f, bbox + f);
-    if (bins.count) bin_face(bins, n, f, bbox[f]);
+    write_chunk_box(packed, live, f, bbox);
   }
   if (zero_fv)
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < a.F * 9; i += stride) zero_fv[i] = 0.f;
@@ -2050,7 +2197,11 @@ static int rast_fwd_prepared(const PRRastArgs& a, const FaceRec* fr, const uint2
   size_t lds = rast_fwd_lds(a.K, sl, nw);
   if (const char* e = getenv("PR_RAST_LDS_MIN")) lds = std::max(lds, (size_t)atol(e));  // occupancy sweeps
   if (lds > 160 * 1024) return set_error(PR_ERR_ARG, "rast_fwd: faces_per_pixel too large for the LDS queue (max 300)");
-  launch_rast_fwd(a, fr, fbox, sl, frag, lds, bins, st, nw);
+  // two-level tile cull over the chunk boxes (PR_RAST_CHUNK_CULL=0, read per call: no chunk is
+  // rejected, i.e. the flat scan of every face box); tiles with a bin list scan that list
+  const char* cc = getenv("PR_RAST_CHUNK_CULL");
+  const int chunk_cull = !(cc && cc[0] == '0');
+  launch_rast_fwd(a, fr, fbox, chunk_cull, sl, frag, lds, bins, st, nw);
   if (int e = check_launch("rast_fwd")) return e;
   if (frag) return PR_OK;
   const int64_t total = (int64_t)a.N * a.H * a.W * a.K;
