@@ -33,6 +33,9 @@
  *   pr_vert_normals_fwd / pr_vert_normals_bwd
  *       PyTorch3D Meshes.verts_normals_packed, the vertex normals phong_shading
  *       interpolates for RandomPhongShader (random_rasterizer.py:60-116).
+ *   pr_mesh_laplacian_fwd / _bwd, pr_mesh_edge_fwd / _bwd
+ *       PyTorch3D mesh_laplacian_smoothing / mesh_edge_loss, the regulariser of the
+ *       vertex-deformation task (experiments/eval.py:454-457).
  */
 #ifndef PERTRENDER_H_
 #define PERTRENDER_H_
@@ -505,6 +508,53 @@ typedef struct PRRgbMseArgs {
 size_t pr_rgb_mse_workspace(int64_t P);  /* floats */
 int pr_rgb_mse_fwd(const PRRgbMseArgs* args, void* stream);
 int pr_rgb_mse_bwd(const PRRgbMseArgs* args, void* stream);
+
+/* Mesh regularisers of the vertex-deformation task (experiments/eval.py:454-457; PyTorch3D 0.4.0
+ * mesh_laplacian_smoothing and mesh_edge_loss) on a packed mesh batch, one lane per vertex, every
+ * sum a gather in a fixed order (no atomics): two calls on the same input give the same bits.
+ * Additive to ABI 21.
+ *   pr_mesh_laplacian_fwd: *loss = sum_i weight[i] |l_i|, weight[i] = 1 / (N V_mesh(i)), with
+ *     UNIFORM  l_i = (1 / max(deg_i, 1)) sum_{j in nbr(i)} v_j - v_i
+ *     COT      l_i = n_i sum_j L_ij v_j - v_i,  n_i = 1 / r_i if r_i > 0 else r_i
+ *     COTCURV  l_i = (sum_j L_ij v_j - r_i v_i) 0.25 (1 / a_i if a_i > 0 else a_i)
+ *     L_ij = the sum over the faces at edge ij of the cotangent at the opposite corner,
+ *     r_i = sum_j L_ij, a_i = the area sum of i's faces; per face with sides A = |v1 - v2|,
+ *     B = |v0 - v2|, C = |v0 - v1|: s = (A + B + C) / 2, area = sqrt(max(s(s-A)(s-B)(s-C), 1e-12)),
+ *     cot_0 = (B^2 + C^2 - A^2) / (4 area), cyclically.  The weights are constants of the backward.
+ *     The forward leaves in `gather` / `diag` the per-vertex terms its backward needs.
+ *   pr_mesh_laplacian_bwd: grad_verts[k] = *grad_loss (sum_i L'_ki gather[i] - diag[k]) (overwritten),
+ *     L' the same weights (1 per neighbour for UNIFORM).
+ *   pr_mesh_edge_fwd: *loss = sum over unique edges ab of weight[a] (|v_a - v_b| - target)^2,
+ *     weight[i] = 1 / (N E_mesh(i)); pr_mesh_edge_bwd its gradient (an edge of length 0 gives 0). */
+#define PR_MESH_LAP_UNIFORM 0
+#define PR_MESH_LAP_COT 1
+#define PR_MESH_LAP_COTCURV 2
+
+typedef struct PRMeshLossArgs {
+  const float* verts;               /* (V,3) */
+  const int64_t* faces;             /* (F,3); COT / COTCURV */
+  int64_t V, F;
+  int32_t method;                   /* PR_MESH_LAP_*; ignored by the edge loss */
+  float target_length;              /* edge loss */
+  const float* weight;              /* (V) per-vertex weight */
+  const int64_t* nbr_start;         /* (V+1) vertex -> unique neighbours, ascending; UNIFORM, edge */
+  const int64_t* nbr;               /* (2E) */
+  const int64_t* vert_corner_start; /* (V+1) vertex -> face corners t = 3 f + c; COT / COTCURV */
+  const int64_t* vert_corners;      /* (3F) */
+  float* face_cot;                  /* (F,4) cot_0, cot_1, cot_2, area: fwd out, bwd in; COT / COTCURV */
+  float* gather;                    /* (V,3) Laplacian fwd out, bwd in */
+  float* diag;                      /* (V,3) Laplacian fwd out, bwd in */
+  float* partials;                  /* fwd workspace: pr_mesh_loss_workspace floats */
+  float* loss;                      /* fwd out, 0-d */
+  const float* grad_loss;           /* bwd in, 0-d */
+  float* grad_verts;                /* bwd out (V,3), overwritten */
+} PRMeshLossArgs;
+
+size_t pr_mesh_loss_workspace(int64_t V);  /* floats */
+int pr_mesh_laplacian_fwd(const PRMeshLossArgs* args, void* stream);
+int pr_mesh_laplacian_bwd(const PRMeshLossArgs* args, void* stream);
+int pr_mesh_edge_fwd(const PRMeshLossArgs* args, void* stream);
+int pr_mesh_edge_bwd(const PRMeshLossArgs* args, void* stream);
 
 int pr_abi_version(void);
 const char* pr_last_error(void);

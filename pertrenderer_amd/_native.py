@@ -152,6 +152,18 @@ class PRNormalsArgs(C.Structure):
                 ("vert_corner_start", _vp), ("vert_corners", _vp)]
 
 
+PR_MESH_LAP_UNIFORM = 0
+PR_MESH_LAP_COT = 1
+PR_MESH_LAP_COTCURV = 2
+
+
+class PRMeshLossArgs(C.Structure):
+    _fields_ = [("verts", _vp), ("faces", _vp), ("V", C.c_int64), ("F", C.c_int64), ("method", C.c_int32),
+                ("target_length", C.c_float), ("weight", _vp), ("nbr_start", _vp), ("nbr", _vp),
+                ("vert_corner_start", _vp), ("vert_corners", _vp), ("face_cot", _vp), ("gather", _vp),
+                ("diag", _vp), ("partials", _vp), ("loss", _vp), ("grad_loss", _vp), ("grad_verts", _vp)]
+
+
 # every symbol include/pertrender.h declares, with its argument struct (None = no args)
 EXPORTS = {
     "pr_abi_version": (C.c_int, []),
@@ -190,6 +202,11 @@ EXPORTS = {
     "pr_shade_bwd": (C.c_int, [C.POINTER(PRShadeArgs), _vp]),
     "pr_vert_normals_fwd": (C.c_int, [C.POINTER(PRNormalsArgs), _vp]),
     "pr_vert_normals_bwd": (C.c_int, [C.POINTER(PRNormalsArgs), _vp]),
+    "pr_mesh_loss_workspace": (C.c_size_t, [C.c_int64]),
+    "pr_mesh_laplacian_fwd": (C.c_int, [C.POINTER(PRMeshLossArgs), _vp]),
+    "pr_mesh_laplacian_bwd": (C.c_int, [C.POINTER(PRMeshLossArgs), _vp]),
+    "pr_mesh_edge_fwd": (C.c_int, [C.POINTER(PRMeshLossArgs), _vp]),
+    "pr_mesh_edge_bwd": (C.c_int, [C.POINTER(PRMeshLossArgs), _vp]),
 }
 ABI_VERSION = 21
 

@@ -71,6 +71,8 @@ class _Topology:
         self._packed = None
         self._idx = None
         self._csr = {}
+        self._edges = self._nedges = self._nbr = self._pairs = self._vmesh = None
+        self._weights = {}
 
     def faces_packed(self):
         if self._packed is None:
@@ -109,6 +111,77 @@ class _Topology:
             start = torch.searchsorted(keys[order].contiguous(), torch.arange(V + 1, device=f.device))
             c = self._csr[kind] = (start.contiguous(), vals[order].contiguous())
         return c
+
+    # ---- caches of the mesh regularisers (renderer/loss.py): built once per topology (building
+    # may synchronise, as torch.unique does), read afterwards without a sync or an index kernel
+    def _edge_keys(self):
+        """(lo, hi) vertex ids of the 3F face edges, edge c = (corner c, corner c+1)."""
+        f = self.faces_packed()
+        a = torch.cat([f[:, 0], f[:, 1], f[:, 2]])
+        b = torch.cat([f[:, 1], f[:, 2], f[:, 0]])
+        return torch.minimum(a, b), torch.maximum(a, b)
+
+    def edges_packed(self):
+        """Unique undirected edges (E,2) int64 with e[:,0] < e[:,1], in lexicographic order."""
+        if self._edges is None:
+            V = sum(self.nverts)
+            lo, hi = self._edge_keys()
+            key = torch.unique(lo * (V + 1) + hi)  # sorted
+            e = torch.stack([key // (V + 1), key % (V + 1)], dim=1)
+            self._edges = e[e[:, 0] < e[:, 1]].contiguous()
+        return self._edges
+
+    def mesh_of_vert(self):
+        """(V,) int64 mesh index of every packed vertex."""
+        if self._vmesh is None:
+            nv = self.index_tensors()["nverts"]
+            self._vmesh = torch.repeat_interleave(torch.arange(len(self.nverts), device=self.device), nv)
+        return self._vmesh
+
+    def num_edges_per_mesh(self):
+        """(N,) int64 edge counts, a device tensor."""
+        if self._nedges is None:
+            e = self.edges_packed()
+            self._nedges = torch.bincount(self.mesh_of_vert()[e[:, 0]], minlength=len(self.nverts))
+        return self._nedges
+
+    def neighbour_csr(self):
+        """(start (V+1), nbr (2E)) int64: the unique neighbours of packed vertex v, ascending, at
+        nbr[start[v]:start[v+1]]."""
+        if self._nbr is None:
+            V = sum(self.nverts)
+            e = self.edges_packed()
+            src, dst = torch.cat([e[:, 0], e[:, 1]]), torch.cat([e[:, 1], e[:, 0]])
+            order = torch.argsort(src * (V + 1) + dst)
+            start = torch.searchsorted(src[order].contiguous(), torch.arange(V + 1, device=e.device))
+            self._nbr = (start.contiguous(), dst[order].contiguous())
+        return self._nbr
+
+    def face_pairs(self):
+        """(a (P), b (P), P): the faces that follow each other in the list of the 3F face edges
+        sorted by their undirected key (mesh_normal_consistency's pairs); P is a Python int."""
+        if self._pairs is None:
+            F, V = self.faces_packed().shape[0], sum(self.nverts)
+            lo, hi = self._edge_keys()
+            fid = torch.arange(F, device=lo.device).repeat(3)
+            key = lo * (V + 1) + hi
+            order = key.argsort()  # the per-call code's sort, so its pairs
+            k, fo = key[order], fid[order]
+            same = k[1:] == k[:-1]
+            a, b = fo[:-1][same].contiguous(), fo[1:][same].contiguous()
+            self._pairs = (a, b, int(a.shape[0]))
+        return self._pairs
+
+    def loss_weights(self, kind):
+        """(V,) float32 per-vertex weight of the native mesh losses: "verts" 1 / (N V_m),
+        "edges" 1 / (N E_m) (0 for a mesh without edges), m the vertex's mesh."""
+        w = self._weights.get(kind)
+        if w is None:
+            n = self.index_tensors()["nverts"] if kind == "verts" else self.num_edges_per_mesh()
+            n = n.to(F32)
+            per_mesh = torch.where(n > 0, (1.0 / n.clamp(min=1.0)) / float(len(self.nverts)), torch.zeros_like(n))
+            w = self._weights[kind] = per_mesh[self.mesh_of_vert()].contiguous()
+        return w
 
 
 class Meshes:
@@ -163,6 +236,21 @@ class Meshes:
     def corner_csr(self, kind="gather"):
         """Vertex -> face-corner CSR of the packed topology (_Topology.corner_csr); not PyTorch3D API."""
         return self._topo.corner_csr(kind)
+
+    def edges_packed(self):
+        """Unique undirected edges (E,2) of the packed topology, cached (_Topology.edges_packed)."""
+        return self._topo.edges_packed()
+
+    def num_edges_per_mesh(self):
+        return self._topo.num_edges_per_mesh()
+
+    def neighbour_csr(self):
+        """Vertex -> unique neighbours CSR of the packed topology, cached; not PyTorch3D API."""
+        return self._topo.neighbour_csr()
+
+    def face_pairs(self):
+        """Face pairs across shared edges, cached (_Topology.face_pairs); not PyTorch3D API."""
+        return self._topo.face_pairs()
 
     def verts_padded(self):
         if len(self._verts) == 1:
