@@ -36,6 +36,9 @@
  *   pr_mesh_laplacian_fwd / _bwd, pr_mesh_edge_fwd / _bwd
  *       PyTorch3D mesh_laplacian_smoothing / mesh_edge_loss, the regulariser of the
  *       vertex-deformation task (experiments/eval.py:454-457).
+ *   pr_mesh_normal_consistency_fwd / _bwd, pr_chamfer_fwd / _bwd
+ *       mesh_normal_consistency and chamfer_distance, the other two losses
+ *       experiments/eval.py:26-31 imports from pytorch3d.loss.
  */
 #ifndef PERTRENDER_H_
 #define PERTRENDER_H_
@@ -555,6 +558,77 @@ int pr_mesh_laplacian_fwd(const PRMeshLossArgs* args, void* stream);
 int pr_mesh_laplacian_bwd(const PRMeshLossArgs* args, void* stream);
 int pr_mesh_edge_fwd(const PRMeshLossArgs* args, void* stream);
 int pr_mesh_edge_bwd(const PRMeshLossArgs* args, void* stream);
+
+/* mesh_normal_consistency of renderer/loss.py (its own definition, not PyTorch3D's per-edge one) on
+ * a packed mesh batch; no atomics, two calls give the same bits.  Additive to ABI 21.
+ *   n_f = c_f / max(|c_f|, 1e-6), c_f = (v1 - v0) x (v2 - v0);
+ *   *loss = (1 / P) sum over the P face pairs (a, b) of 1 - n_a . n_b.
+ * The pairs come as a CSR over faces in which pair (a, b) stands in a's row (partner b) and in b's
+ * row (partner a).  The forward leaves n_f and the row sums s_f = sum of the partners' normals for
+ * the backward: d loss / d n_f = -(*grad_loss / P) s_f, through the normalisation
+ * (g_c = (g_n - n (n . g_n)) / |c| where |c| >= 1e-6, g_n / 1e-6 otherwise: torch's clamp_min) and
+ * the cross product to the corners, then gathered per vertex over the corner CSR.  P = 0 is the
+ * caller's case (the loss is 0): both entry points reject it. */
+typedef struct PRNormalConsistencyArgs {
+  const float* verts;               /* (V,3) */
+  const int64_t* faces;             /* (F,3) */
+  int64_t V, F, P;                  /* P: face pairs */
+  const int64_t* pair_start;        /* (F+1) face -> partner faces, in ascending pair index; fwd */
+  const int64_t* pair_partner;      /* (2P) */
+  const int64_t* vert_corner_start; /* (V+1) vertex -> face corners t = 3 f + c, ascending; bwd */
+  const int64_t* vert_corners;      /* (3F) */
+  float* face_normal;               /* (F,4) n_f and 1 / max(|c_f|, 1e-6), negated where the clamp is
+                                       active: fwd out, bwd in */
+  float* face_sum;                  /* (F,3) s_f: fwd out, bwd in */
+  float* face_grad;                 /* (F,3) bwd scratch: d loss / d c_f */
+  float* partials;                  /* fwd workspace: pr_mesh_loss_workspace(F) floats */
+  float* loss;                      /* fwd out, 0-d */
+  const float* grad_loss;           /* bwd in, 0-d */
+  float* grad_verts;                /* bwd out (V,3), overwritten */
+} PRNormalConsistencyArgs;
+
+int pr_mesh_normal_consistency_fwd(const PRNormalConsistencyArgs* args, void* stream);
+int pr_mesh_normal_consistency_bwd(const PRNormalConsistencyArgs* args, void* stream);
+
+/* Squared nearest-neighbour distances between padded point clouds x (N,P,3) and y (N,Q,3), both
+ * directions per call (the core of PyTorch3D 0.4.0 chamfer_distance).  Additive to ABI 21.
+ *   pr_chamfer_fwd: dist_x[n,i] = min over j < y_len[n] of |x_i - y_j|^2, idx_x[n,i] the lowest j
+ *     that attains it (d^2 is the sum of the squared coordinate differences: a point on top of its
+ *     neighbour gives exactly 0); dist_y / idx_y the mirror.  A point at or past its cloud's
+ *     length, or with an empty other cloud, gets dist 0 and idx -1.  A NaN database point is never
+ *     chosen; a live point for which no d^2 compares below +inf (NaN or overflowing coordinates)
+ *     gets a non-finite dist (NaN if the point itself is NaN, else +inf), idx -1 and gradient 0,
+ *     where torch.min would propagate the NaN.  The lengths are device
+ *     arrays read by the kernels (NULL: full length); values are clamped to [0, P] / [0, Q].
+ *     With few queries and many database points the database is cut into ranges over a further
+ *     grid dimension (count chosen from the shape; PR_CHAMFER_SPLITS overrides it, read per call)
+ *     and the partial results merged through `workspace`, in range order with the same tie rule.
+ *   pr_chamfer_bwd: grad_x[n,i] = 2 grad_dist_x[n,i] (x_i - y_idx_x[i])
+ *       + sum over j ascending with idx_y[n,j] = i of 2 grad_dist_y[n,j] (x_i - y_j)  (overwritten),
+ *     grad_y the mirror; points with idx -1 and padded points get 0.  No atomics, a fixed order: the
+ *     j are cut into the same ranges as the forward's database, each range summed in ascending j
+ *     and the ranges added in order through `workspace`. */
+typedef struct PRChamferArgs {
+  const float* x;            /* (N,P,3) */
+  const float* y;            /* (N,Q,3) */
+  const int64_t* x_len;      /* (N) or NULL */
+  const int64_t* y_len;      /* (N) or NULL */
+  int64_t N, P, Q;
+  float* dist_x;             /* (N,P) fwd out */
+  float* dist_y;             /* (N,Q) fwd out */
+  int32_t* idx_x;            /* (N,P) fwd out, bwd in */
+  int32_t* idx_y;            /* (N,Q) fwd out, bwd in */
+  void* workspace;           /* fwd and bwd: pr_chamfer_workspace bytes (may be NULL when that is 0) */
+  size_t workspace_bytes;
+  const float* grad_dist_x;  /* (N,P) bwd in */
+  const float* grad_dist_y;  /* (N,Q) bwd in */
+  float* grad_x;             /* (N,P,3) bwd out */
+  float* grad_y;             /* (N,Q,3) bwd out */
+} PRChamferArgs;
+
+size_t pr_chamfer_workspace(int64_t N, int64_t P, int64_t Q);  /* bytes; 0 when no range split */
+int pr_chamfer_fwd(const PRChamferArgs* args, void* stream);
+int pr_chamfer_bwd(const PRChamferArgs* args, void* stream);
 
 int pr_abi_version(void);
 const char* pr_last_error(void);

@@ -164,6 +164,20 @@ class PRMeshLossArgs(C.Structure):
                 ("diag", _vp), ("partials", _vp), ("loss", _vp), ("grad_loss", _vp), ("grad_verts", _vp)]
 
 
+class PRNormalConsistencyArgs(C.Structure):
+    _fields_ = [("verts", _vp), ("faces", _vp), ("V", C.c_int64), ("F", C.c_int64), ("P", C.c_int64),
+                ("pair_start", _vp), ("pair_partner", _vp), ("vert_corner_start", _vp), ("vert_corners", _vp),
+                ("face_normal", _vp), ("face_sum", _vp), ("face_grad", _vp), ("partials", _vp), ("loss", _vp),
+                ("grad_loss", _vp), ("grad_verts", _vp)]
+
+
+class PRChamferArgs(C.Structure):
+    _fields_ = [("x", _vp), ("y", _vp), ("x_len", _vp), ("y_len", _vp), ("N", C.c_int64), ("P", C.c_int64),
+                ("Q", C.c_int64), ("dist_x", _vp), ("dist_y", _vp), ("idx_x", _vp), ("idx_y", _vp),
+                ("workspace", _vp), ("workspace_bytes", C.c_size_t), ("grad_dist_x", _vp), ("grad_dist_y", _vp),
+                ("grad_x", _vp), ("grad_y", _vp)]
+
+
 # every symbol include/pertrender.h declares, with its argument struct (None = no args)
 EXPORTS = {
     "pr_abi_version": (C.c_int, []),
@@ -207,6 +221,11 @@ EXPORTS = {
     "pr_mesh_laplacian_bwd": (C.c_int, [C.POINTER(PRMeshLossArgs), _vp]),
     "pr_mesh_edge_fwd": (C.c_int, [C.POINTER(PRMeshLossArgs), _vp]),
     "pr_mesh_edge_bwd": (C.c_int, [C.POINTER(PRMeshLossArgs), _vp]),
+    "pr_mesh_normal_consistency_fwd": (C.c_int, [C.POINTER(PRNormalConsistencyArgs), _vp]),
+    "pr_mesh_normal_consistency_bwd": (C.c_int, [C.POINTER(PRNormalConsistencyArgs), _vp]),
+    "pr_chamfer_workspace": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    "pr_chamfer_fwd": (C.c_int, [C.POINTER(PRChamferArgs), _vp]),
+    "pr_chamfer_bwd": (C.c_int, [C.POINTER(PRChamferArgs), _vp]),
 }
 ABI_VERSION = 21
 

@@ -13,6 +13,10 @@
 // and the backward is the forward's gather over them.  Both gather over the corners of vertex i:
 // in face (i, j, k) the corner adds cot_k x_j + cot_j x_k (the cot at a corner weighs the edge
 // opposite to it), which needs no edge -> face map.
+//
+// mesh_normal_consistency (loss.py's definition) follows the same scheme one level up: one lane per
+// face over the face-pair CSR forward (3 launches), one lane per face and then one per vertex over
+// the corner CSR backward (2 launches), instead of the ~100 torch kernels of the composition.
 #include "pr_common.h"
 
 namespace pr {
@@ -173,6 +177,77 @@ __global__ void __launch_bounds__(kThreads) edge_bwd_kernel(PRMeshLossArgs a) {
   }
 }
 
+// ---- normal consistency: loss = (1/P) sum over the face pairs (a, b) of 1 - n_a . n_b with
+// n_f = c_f / max(|c_f|, eps), c_f = (v1 - v0) x (v2 - v0) (loss.py's composition, not PyTorch3D's
+// per-edge formula).  Every pair stands in the CSR rows of both of its faces, so a face's row sum
+// s_f = sum of its partners' normals is d (sum of cosines) / d n_f, and half the row sums of
+// 1 - n_f . n_p add up to the pair sum.
+constexpr float kNormalEps = 1e-6f;
+
+PR_DEV F3 cross3(F3 a, F3 b) { return F3{a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+PR_DEV float dot3(F3 a, F3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
+PR_DEV F3 load3of4(const float* p, int64_t i) { return F3{p[i * 4], p[i * 4 + 1], p[i * 4 + 2]}; }
+
+// per face: n_f and 1 / max(|c_f|, eps), the latter negated where the clamp is active
+__global__ void __launch_bounds__(kThreads) face_normal_kernel(PRNormalConsistencyArgs a) {
+  for (int64_t f = (int64_t)blockIdx.x * kThreads + threadIdx.x; f < a.F; f += (int64_t)gridDim.x * kThreads) {
+    const F3 v0 = load3(a.verts, a.faces[f * 3]), v1 = load3(a.verts, a.faces[f * 3 + 1]),
+             v2 = load3(a.verts, a.faces[f * 3 + 2]);
+    const F3 c = cross3(sub(v1, v0), sub(v2, v0));
+    const float len = norm3(c), den = fmaxf(len, kNormalEps);
+    a.face_normal[f * 4] = c.x / den;
+    a.face_normal[f * 4 + 1] = c.y / den;
+    a.face_normal[f * 4 + 2] = c.z / den;
+    a.face_normal[f * 4 + 3] = len >= kNormalEps ? 1.f / den : -1.f / den;
+  }
+}
+
+__global__ void __launch_bounds__(kThreads) normal_pairs_kernel(PRNormalConsistencyArgs a) {
+  float acc = 0.f;
+  for (int64_t f = (int64_t)blockIdx.x * kThreads + threadIdx.x; f < a.F; f += (int64_t)gridDim.x * kThreads) {
+    const F3 n = load3of4(a.face_normal, f);
+    F3 s{0.f, 0.f, 0.f};
+    float t = 0.f;
+    for (int64_t j = a.pair_start[f]; j < a.pair_start[f + 1]; ++j) {
+      const F3 p = load3of4(a.face_normal, a.pair_partner[j]);
+      acc3(s, p);
+      t += 1.f - dot3(n, p);  // the 1 - cos terms, not the cosines: they do not cancel on a smooth mesh
+    }
+    store3(a.face_sum, f, s);
+    acc += t;
+  }
+  block_partial(acc * (0.5f / (float)a.P), a.partials);
+}
+
+// per face: d loss / d c_f from d loss / d n_f = -(g / P) s_f, through the normalisation
+__global__ void __launch_bounds__(kThreads) normal_face_bwd_kernel(PRNormalConsistencyArgs a) {
+  const float g = -*a.grad_loss / (float)a.P;
+  for (int64_t f = (int64_t)blockIdx.x * kThreads + threadIdx.x; f < a.F; f += (int64_t)gridDim.x * kThreads) {
+    const F3 n = load3of4(a.face_normal, f), gn = scale3(load3(a.face_sum, f), g);
+    const float inv = a.face_normal[f * 4 + 3];
+    // |c| >= eps: (g_n - n (n . g_n)) / |c|; clamped: g_n / eps (torch's clamp_min passes nothing to |c|)
+    const F3 gc = inv > 0.f ? scale3(sub(gn, scale3(n, dot3(n, gn))), inv) : scale3(gn, -inv);
+    store3(a.face_grad, f, gc);
+  }
+}
+
+// per vertex over its face corners: c = e1 x e2, e1 = v1 - v0, e2 = v2 - v0, so d/d v1 = e2 x g_c,
+// d/d v2 = g_c x e1 and d/d v0 = minus both
+__global__ void __launch_bounds__(kThreads) normal_vert_bwd_kernel(PRNormalConsistencyArgs a) {
+  for (int64_t v = (int64_t)blockIdx.x * kThreads + threadIdx.x; v < a.V; v += (int64_t)gridDim.x * kThreads) {
+    F3 s{0.f, 0.f, 0.f};
+    for (int64_t j = a.vert_corner_start[v]; j < a.vert_corner_start[v + 1]; ++j) {
+      const int64_t t = a.vert_corners[j], f = t / 3;
+      const int c = (int)(t - f * 3);
+      const F3 v0 = load3(a.verts, a.faces[f * 3]), gc = load3(a.face_grad, f);
+      const F3 d1 = cross3(sub(load3(a.verts, a.faces[f * 3 + 2]), v0), gc);
+      const F3 d2 = cross3(gc, sub(load3(a.verts, a.faces[f * 3 + 1]), v0));
+      acc3(s, c == 1 ? d1 : (c == 2 ? d2 : F3{-d1.x - d2.x, -d1.y - d2.y, -d1.z - d2.z}));
+    }
+    store3(a.grad_verts, v, s);
+  }
+}
+
 int loss_blocks(int64_t n) {
   return (int)std::max<int64_t>(1, std::min<int64_t>((n + kThreads - 1) / kThreads, kLossBlocks));
 }
@@ -194,6 +269,19 @@ int mesh_check(const PRMeshLossArgs* a, const char* what, bool laplacian, bool f
   if (laplacian && (!a->gather || !a->diag)) return set_error(PR_ERR_ARG, w + ": gather / diag missing");
   if (fwd && (!a->partials || !a->loss)) return set_error(PR_ERR_ARG, w + ": loss / workspace missing");
   if (!fwd && (!a->grad_loss || !a->grad_verts)) return set_error(PR_ERR_ARG, w + ": grads missing");
+  return PR_OK;
+}
+
+int normal_check(const PRNormalConsistencyArgs* a, const char* what, bool fwd) {
+  const std::string w(what);
+  if (!a) return set_error(PR_ERR_ARG, w + ": null args");
+  if (a->V <= 0 || a->F <= 0 || a->P <= 0) return set_error(PR_ERR_ARG, w + ": V, F and P must be positive");
+  if (!a->verts || !a->faces) return set_error(PR_ERR_ARG, w + ": verts / faces missing");
+  if (!a->face_normal || !a->face_sum) return set_error(PR_ERR_ARG, w + ": face_normal / face_sum missing");
+  if (fwd && (!a->pair_start || !a->pair_partner)) return set_error(PR_ERR_ARG, w + ": face-pair CSR missing");
+  if (fwd && (!a->partials || !a->loss)) return set_error(PR_ERR_ARG, w + ": loss / workspace missing");
+  if (!fwd && (!a->vert_corner_start || !a->vert_corners)) return set_error(PR_ERR_ARG, w + ": corner CSR missing");
+  if (!fwd && (!a->grad_loss || !a->face_grad || !a->grad_verts)) return set_error(PR_ERR_ARG, w + ": grads missing");
   return PR_OK;
 }
 
@@ -253,4 +341,27 @@ extern "C" int pr_mesh_edge_bwd(const PRMeshLossArgs* args, void* stream) {
   edge_bwd_kernel<<<(int)std::min<int64_t>((a.V + kThreads - 1) / kThreads, 4096), kThreads, 0,
                     reinterpret_cast<hipStream_t>(stream)>>>(a);
   return check_launch("mesh_edge_bwd");
+}
+
+extern "C" int pr_mesh_normal_consistency_fwd(const PRNormalConsistencyArgs* args, void* stream) {
+  if (int e = normal_check(args, "mesh_normal_consistency_fwd", true)) return e;
+  const PRNormalConsistencyArgs& a = *args;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int nb = loss_blocks(a.F);
+  face_normal_kernel<<<nb, kThreads, 0, st>>>(a);
+  if (int e = check_launch("mesh_face_normal")) return e;
+  normal_pairs_kernel<<<nb, kThreads, 0, st>>>(a);
+  if (int e = check_launch("mesh_normal_pairs")) return e;
+  mesh_finalize_kernel<<<1, kThreads, 0, st>>>(a.partials, nb, a.loss);
+  return check_launch("mesh_finalize");
+}
+
+extern "C" int pr_mesh_normal_consistency_bwd(const PRNormalConsistencyArgs* args, void* stream) {
+  if (int e = normal_check(args, "mesh_normal_consistency_bwd", false)) return e;
+  const PRNormalConsistencyArgs& a = *args;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  normal_face_bwd_kernel<<<(int)std::min<int64_t>((a.F + kThreads - 1) / kThreads, 4096), kThreads, 0, st>>>(a);
+  if (int e = check_launch("mesh_normal_face_bwd")) return e;
+  normal_vert_bwd_kernel<<<(int)std::min<int64_t>((a.V + kThreads - 1) / kThreads, 4096), kThreads, 0, st>>>(a);
+  return check_launch("mesh_normal_vert_bwd");
 }

@@ -71,7 +71,7 @@ class _Topology:
         self._packed = None
         self._idx = None
         self._csr = {}
-        self._edges = self._nedges = self._nbr = self._pairs = self._vmesh = None
+        self._edges = self._nedges = self._nbr = self._pairs = self._pair_csr = self._vmesh = None
         self._weights = {}
 
     def faces_packed(self):
@@ -171,6 +171,20 @@ class _Topology:
             a, b = fo[:-1][same].contiguous(), fo[1:][same].contiguous()
             self._pairs = (a, b, int(a.shape[0]))
         return self._pairs
+
+    def face_pair_csr(self):
+        """(start (F+1), partner (2P)) int64: face_pairs() as a CSR over faces.  Pair k = (a, b)
+        stands in a's row with partner b and in b's row with partner a; a row lists its partners in
+        ascending pair index (an edge shared by three faces gives two pairs, as in face_pairs())."""
+        if self._pair_csr is None:
+            a, b, npairs = self.face_pairs()
+            F = self.faces_packed().shape[0]
+            src, dst = torch.cat([a, b]), torch.cat([b, a])
+            k = torch.arange(npairs, device=a.device).repeat(2)
+            order = torch.argsort(src * max(npairs, 1) + k)
+            start = torch.searchsorted(src[order].contiguous(), torch.arange(F + 1, device=a.device))
+            self._pair_csr = (start.contiguous(), dst[order].contiguous())
+        return self._pair_csr
 
     def loss_weights(self, kind):
         """(V,) float32 per-vertex weight of the native mesh losses: "verts" 1 / (N V_m),
