@@ -81,10 +81,10 @@ def test_aggregate_plane_gradients_match_oracle(device):
 
 
 def test_soft_blend_plane_gradients_match_oracle(device):
-    from test_gpu_softblend import _frags
+    from softblend_cases import plain_frags
     N, H, W, K = 2, 10, 8, 12
     sigma, gamma, alpha, eps, bg = 1e-3, 1e-2, 1.3, 1e-10, (0.1, 0.2, 0.3)
-    p2f, d, z, cols, gimg, valid = _frags(N, H, W, K, 17, True, sigma)
+    p2f, d, z, cols, gimg, valid = plain_frags(N, H, W, K, 17, True, sigma)
     zn, zf = _planes(N, False, device)
     ozn, ozf = (t.detach().cpu().clone().requires_grad_(True) for t in (zn, zf))
     oimg, og = bo.soft_blend_forward_backward(p2f, d, z, cols, sigma, gamma, alpha, eps, bg, ozn, ozf, gimg)
