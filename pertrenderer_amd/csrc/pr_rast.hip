@@ -454,6 +454,9 @@ PR_DEV bool in_bbox(const FaceRec& r, V2 p) {
 constexpr unsigned kProfTiles = 1 << 16;
 __device__ long long g_rast_prof[kProfTiles * 16];  // per tile: x y z list t0 t1 hwid stamps[6] SL
 #define PR_STAMP(i) (stamp[i] += (long long)__builtin_amdgcn_s_memtime() - t_, t_ = __builtin_amdgcn_s_memtime())
+// rast_bwd_kernel, per tile: x y z slots t0 t1 hwid stamps[5] rounds faces (d zbuf | d dists << 32 non-zero)
+// (d bary non-zero | all-zero slots << 32)
+__device__ long long g_rast_bwd_prof[kProfTiles * 16];
 #else
 #define PR_STAMP(i) ((void)0)
 #endif
@@ -1587,27 +1590,36 @@ PR_DEV void acc_seg(V2 p, V2 a, V2 b, float g, float* ga, float* gb) {  // squar
   gb[0] += g * t * 2.f * dx;         gb[1] += g * t * 2.f * dy;
 }
 
-PR_DEV void slot_grad_exact(const PRRastArgs& a, V2 p, const float* v, int64_t o, float out[9]) {
+// gd_zero: the caller has read d dists of this slot as +-0.  The distance term is then g * x with
+// g = +-0, which is +-0 for finite x, and 0.f + (+-0) leaves the accumulators at their starting +0:
+// the block is skipped with the same bits.  x is finite whenever the face's screen coordinates are
+// below 1e9 in magnitude (no overflow in the squared edge length, so t is a finite number in [0, 1]);
+// a face with a larger, infinite or NaN coordinate runs the block as written.
+PR_DEV void slot_grad_exact(const PRRastArgs& a, V2 p, const float* v, int64_t o, float out[9], bool gd_zero = false) {
   const V2 v0{v[0], v[1]}, v1{v[3], v[4]}, v2{v[6], v[7]};
   const float z0 = v[2], z1 = v[5], z2 = v[8];
   const bool persp = a.perspective_correct != 0, clip = a.clip_barycentric_coords != 0;
-  const float gzb = a.grad_zbuf ? a.grad_zbuf[o] : 0.f;
-  const float gd = a.grad_dists ? a.grad_dists[o] : 0.f;
-  float gbu[3] = {0.f, 0.f, 0.f};
-  if (a.grad_bary) { gbu[0] = a.grad_bary[o * 3]; gbu[1] = a.grad_bary[o * 3 + 1]; gbu[2] = a.grad_bary[o * 3 + 2]; }
   float bw[3], bp[3], bc[3];
   bary_fwd(p, v0, v1, v2, bw);
   if (persp) persp_fwd(bw, z0, z1, z2, bp); else { bp[0] = bw[0]; bp[1] = bw[1]; bp[2] = bw[2]; }
   if (clip) clip_fwd(bp, bc); else { bc[0] = bp[0]; bc[1] = bp[1]; bc[2] = bp[2]; }
   const bool inside = bp[0] > 0.f && bp[1] > 0.f && bp[2] > 0.f;
   float gv[3][2] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};
-  {
+  constexpr float kTame = 1e9f;
+  const bool tame = fabsf(v0.x) < kTame && fabsf(v0.y) < kTame && fabsf(v1.x) < kTame && fabsf(v1.y) < kTame &&
+                    fabsf(v2.x) < kTame && fabsf(v2.y) < kTame && fabsf(z0) < INFINITY && fabsf(z1) < INFINITY &&
+                    fabsf(z2) < INFINITY;
+  if (!(gd_zero && tame)) {
+    const float gd = a.grad_dists ? a.grad_dists[o] : 0.f;
     const float g = inside ? -gd : gd;
     const float e01 = seg_dist2(p, v0, v1), e02 = seg_dist2(p, v0, v2), e12 = seg_dist2(p, v1, v2);
     if (e01 <= e02 && e01 <= e12) acc_seg(p, v0, v1, g, gv[0], gv[1]);
     else if (e02 <= e01 && e02 <= e12) acc_seg(p, v0, v2, g, gv[0], gv[2]);
     else acc_seg(p, v1, v2, g, gv[1], gv[2]);
   }
+  const float gzb = a.grad_zbuf ? a.grad_zbuf[o] : 0.f;
+  float gbu[3] = {0.f, 0.f, 0.f};
+  if (a.grad_bary) { gbu[0] = a.grad_bary[o * 3]; gbu[1] = a.grad_bary[o * 3 + 1]; gbu[2] = a.grad_bary[o * 3 + 2]; }
   const float gsum[3] = {gbu[0] + gzb * z0, gbu[1] + gzb * z1, gbu[2] + gzb * z2};
   float gpp[3] = {gsum[0], gsum[1], gsum[2]};
   if (clip) {
@@ -1690,95 +1702,176 @@ __global__ void rast_bwd_sorted_grad_kernel(PRRastArgs a, const uint32_t* keys, 
   }
 }
 
-constexpr int kHash = 512;      // LDS hash entries per workgroup (distinct faces of one tile)
+constexpr int kHash = 256;      // LDS hash entries per workgroup (distinct faces of one tile; kBwdFaces are reduced in LDS)
 constexpr int kBwdTile = 8;     // tile width; rows per tile (<= 8) chosen at launch
 constexpr int kBwdThreads = 256;
-#ifndef PR_BWD_ENT  // sweeps: -DPR_BWD_ENT=256 / 1024 measured 46.8 / 77 us vs 44 us at 512
-#define PR_BWD_ENT 512
+// Slots scanned (and at most valid) per round, and the waves per SIMD the register allocation aims
+// at (DESIGN 4 "Backward" has the footprint arithmetic and the measurements).
+#ifndef PR_BWD_ENT
+#define PR_BWD_ENT 256
 #endif
-constexpr int kBwdEnt = PR_BWD_ENT;  // slots scanned (and at most valid) per round: 2 per thread
+#ifndef PR_BWD_WAVES
+#define PR_BWD_WAVES 6
+#endif
+constexpr int kBwdEnt = PR_BWD_ENT;
 constexpr int kBwdFaces = 128;  // faces per tile reduced by the transpose; later ones use global atomics
+constexpr int kBwdSplit = kBwdThreads / kBwdFaces;  // transpose lanes per face
+#ifndef PR_BWD_ROT  // sweeps: 0 leaves every row of tiles in place
+#define PR_BWD_ROT 5
+#endif
+constexpr unsigned kBwdRot = PR_BWD_ROT;  // columns a group of 8 tile rows is rotated by against the one before
+constexpr uint32_t kBwdNoHash = 1023;               // clist hash-slot field of a face the hash could not hold
+static_assert(kBwdEnt % kBwdThreads == 0 && kBwdEnt <= 65535, "round size");
+static_assert(kHash <= (int)kBwdNoHash, "hash slot field");
+
+#ifdef PR_RAST_PROFILE
+PR_DEV void bwd_prof_record(long long rt0, const long long* stamp, int tile_x, int tile_y, int total, int rounds, int nface,
+                            const int* pcount) {
+  unsigned hw, xcc;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc));
+  const unsigned t = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
+  if (t >= kProfTiles) return;
+  long long* rec = g_rast_bwd_prof + (size_t)t * 16;
+  rec[0] = tile_x; rec[1] = tile_y; rec[2] = blockIdx.z; rec[3] = total;
+  rec[4] = rt0; rec[5] = (long long)__builtin_amdgcn_s_memrealtime();
+  rec[6] = (long long)hw | ((long long)(xcc & 0xf) << 32);
+  for (int i = 0; i < 5; ++i) rec[7 + i] = stamp[i];
+  rec[12] = rounds; rec[13] = nface;
+  rec[14] = (long long)pcount[0] | ((long long)pcount[1] << 32);
+  rec[15] = (long long)pcount[2] | ((long long)pcount[3] << 32);
+}
+#endif
 
 // One 256-thread workgroup per 8 x tile_rows pixel tile (tile_rows <= 8), rounds of
 // kBwdEnt slots.  No per-slot atomics on the gradient values (LDS float atomics cost
 // ~4 cycles per lane on gfx950, and a slot has 9 components):
+//  0. wave 0 reads the tile's valid-prefix counts and scans them; a tile without a valid
+//     slot leaves here, before any LDS initialisation.
 //  1. scan: the round's slots (tile rows are contiguous ncols*K slot ranges: coalesced
-//     p2f reads) are compacted into an LDS list of the valid ones (wave ballot, one
-//     LDS append per wave); each new face id gets a tile-local index through an LDS
-//     hash (one CAS per slot, a second atomic per distinct face).
+//     p2f reads) are compacted into an LDS list of the valid ones (wave ballots, one LDS
+//     append per wave and group): slots whose d dists is not +-0 fill the list from the
+//     front, the others from the back, so that step 2 runs the distance term for whole
+//     waves or not at all (one wave per round straddles the split).  Each new face id gets
+//     a tile-local index through an LDS hash (one CAS per slot, a second atomic per distinct
+//     face); the entry keeps its hash slot, which names both the face and its local index.
 //  2. gradient: one lane per valid slot, densely: the 9 vertex-gradient components go
 //     to gbuf[entry] (plain LDS stores) and the entry index to M[face][pixel] (a pixel
 //     holds a face at most once, so every (face, pixel) cell has one writer).
-//  3. transpose: the owner lane of each tile-local face walks its M row (the tile's
-//     pixels) and sums its entries' gbuf rows in registers.
-//  4. after the last round the owners' sums go to LDS and the flush adds each (face,
-//     component) once to global memory, lane-contiguously (global float atomics run at
-//     the memory side; 64 lanes on 64 scattered rows collapse that rate — MI355X guide,
+//  3. transpose: kBwdSplit owner lanes per tile-local face walk alternate pixel quads of
+//     its M row and sum their entries' gbuf rows in registers (pixel order: the same
+//     sums on every launch).
+//  4. after the last round the flush adds each (face, component), the sum of its owners'
+//     partial sums (kept in LDS between the rounds), once to global memory, lane-contiguously (global float atomics run
+//     at the memory side; 64 lanes on 64 scattered rows collapse that rate — MI355X guide,
 //     Global float atomics).
 // Faces past the first kBwdFaces of a tile, and hash overflow, add their slots straight
 // to global memory (correct, slower; dense meshes under large tiles only).
 template <int ROWS, bool EXACT>
-__global__ void __launch_bounds__(kBwdThreads) rast_bwd_kernel(PRRastArgs a, int order) {
+__global__ void __launch_bounds__(kBwdThreads, PR_BWD_WAVES) rast_bwd_kernel(PRRastArgs a, int order) {
   constexpr int tile_rows = ROWS, TP = kBwdTile * ROWS;  // tile pixels
+  static_assert(TP <= 64, "one wave scans the pixel counts; the clist pixel field has 6 bits");
   __shared__ int hkey[kHash];
   __shared__ int hfl[kHash];                      // tile-local face index of a hash entry
   __shared__ int flist[kBwdFaces];                // face id of each tile-local index
-  // [pixel / 4][face][pixel % 4] -> entry index of this round: the transpose's owner lanes (one
-  // per face) read 4 pixels' entries as one 8-B word at consecutive addresses (the [face][pixel]
-  // layout put the lanes 32 B apart: 8-way bank conflicts)
+  // [pixel / 4][face][pixel % 4] -> entry index of this round: the transpose's owner lanes read
+  // 4 pixels' entries as one 8-B word at consecutive addresses (the [face][pixel] layout put the
+  // lanes 32 B apart: 8-way bank conflicts)
   __shared__ alignas(8) uint16_t M[kBwdFaces * TP];
-  __shared__ float gbuf[9 * kBwdEnt];             // [component][entry]; reused for the sums
-  __shared__ int2 clist[kBwdEnt];                 // (pixel << 16 | k, face id)
-  __shared__ int ccount, nface;
+  __shared__ float gbuf[9 * kBwdEnt];             // [component][entry]
+  // [component][owner lane]: the owners' running sums live here between the rounds' transposes, not
+  // in registers across the slot arithmetic (9 VGPRs more there cost a wave of occupancy)
+  __shared__ float sums[9 * kBwdThreads];
+  __shared__ uint32_t clist[kBwdEnt];             // pixel << 20 | k << 10 | hash slot (kBwdNoHash: none)
+  __shared__ int cfront, cback, nface;            // entries with / without a distance term this round
   __shared__ float pxs[kBwdTile], pys[ROWS];
-  __shared__ int pcnt[kBwdTile * ROWS];           // valid-prefix counts of the tile's pixels (or K)
-  __shared__ int pstart[kBwdTile * ROWS + 1];     // exclusive prefix sum of pcnt
+  __shared__ int pstart[kBwdTile * ROWS + 1];     // exclusive prefix sum of the pixels' valid counts
   const int tid = threadIdx.x, lane = tid & 63;
   const int K = a.K, H = a.H, W = a.W;
-  const int n = blockIdx.z, col0 = blockIdx.x * kBwdTile;
+  // Tile of this workgroup.  Consecutive workgroups go to the XCDs in turn and, inside an XCD, to
+  // its CUs in turn, so with a row of 32 tiles a CU keeps meeting the same tile column: on the
+  // bench frame (a disc: the outer columns are empty) the per-tile timeline showed CUs with no
+  // valid slot at all beside CUs with 1.7 times the mean.  Each group of 8 rows is therefore
+  // rotated by a further kBwdRot columns (a bijection of the row, whatever the grid).
+  const int n = blockIdx.z;
+  const int tile_x = order ? (int)((blockIdx.x + kBwdRot * (blockIdx.y >> 3)) % gridDim.x) : (int)blockIdx.x;
+  const int col0 = tile_x * kBwdTile;
   const int row0 = (order ? centre_out(blockIdx.y, gridDim.y) : (int)blockIdx.y) * tile_rows;
   const int ncols = min(kBwdTile, W - col0), nrows = min(tile_rows, H - row0);
   const int64_t tile_o = (((int64_t)n * H + row0) * W + col0) * K;  // slot offset of the tile's first row
   const int64_t row_stride = (int64_t)W * K;
+#ifdef PR_RAST_PROFILE
+  __shared__ int pcount[4];  // slots with d zbuf, d dists, d bary non-zero; with all three zero
+  long long stamp[5] = {0, 0, 0, 0, 0}, t_ = __builtin_amdgcn_s_memtime();
+  const long long rt0 = __builtin_amdgcn_s_memrealtime();
+  int rounds = 0;
+  if (tid < 4) pcount[tid] = 0;
+#endif
+  // ---- 0. valid-prefix counts of the tile's pixels (or K), scanned by wave 0
+  if (tid < 64) {
+    int cnt = 0;
+    if (tid < TP) {
+      const int r = tid / kBwdTile, c = tid - r * kBwdTile;
+      if (r < nrows && c < ncols) cnt = a.pix_count ? a.pix_count[((int64_t)n * H + row0 + r) * W + col0 + c] : K;
+    }
+    int incl = cnt;
+#pragma unroll
+    for (int d = 1; d < TP; d <<= 1) {
+      const int up = __shfl_up(incl, d);
+      if (lane >= d) incl += up;
+    }
+    if (tid < TP) pstart[tid] = incl - cnt;
+    if (tid == TP - 1) pstart[TP] = incl;
+  }
+  __syncthreads();
+  // the rounds walk the tile's valid-prefix slots only (pixel q's slots 0..count-1 are
+  // entries pstart[q].. of the walk): a tile with <= kBwdEnt valid slots is one round
+  const int total = pstart[TP];
+  if (total == 0) {
+#ifdef PR_RAST_PROFILE
+    PR_STAMP(0);
+    if (tid == 0) bwd_prof_record(rt0, stamp, tile_x, row0 / tile_rows, 0, 0, 0, pcount);
+#endif
+    return;
+  }
   for (int i = tid; i < kHash; i += kBwdThreads) hkey[i] = -1;
   for (int i = tid; i < kBwdFaces * TP; i += kBwdThreads) M[i] = 0xffff;
   if (tid < kBwdTile) pxs[tid] = ndc(W - 1 - min(col0 + tid, W - 1), W, H);
   if (tid >= 64 && tid < 64 + ROWS) pys[tid - 64] = ndc(H - 1 - min(row0 + tid - 64, H - 1), H, W);
   if (tid == 0) nface = 0;
-  if (tid < TP) {
-    const int r = tid / kBwdTile, c = tid - r * kBwdTile;
-    pcnt[tid] = (r < nrows && c < ncols) ? (a.pix_count ? a.pix_count[((int64_t)n * H + row0 + r) * W + col0 + c] : K) : 0;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    int acc_s = 0;
-    for (int q = 0; q < TP; ++q) { pstart[q] = acc_s; acc_s += pcnt[q]; }
-    pstart[TP] = acc_s;
-  }
-  __syncthreads();
-  // the rounds walk the tile's valid-prefix slots only (pixel q's slots 0..pcnt[q]-1 are
-  // entries pstart[q].. of the walk): a tile with <= kBwdEnt valid slots is one round
-  const int total = pstart[TP];
-  float acc[9] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};  // owner lane tid < kBwdFaces
+#pragma unroll
+  for (int cc = 0; cc < 9; ++cc) sums[cc * kBwdThreads + tid] = 0.f;
+  // transpose owner: face tid % kBwdFaces, pixel quads tid / kBwdFaces, + kBwdSplit, ...
+  const int own_fl = tid % kBwdFaces, own_part = tid / kBwdFaces;
+  PR_STAMP(0);
   for (int c0 = 0; c0 < total; c0 += kBwdEnt) {
-    if (tid == 0) ccount = 0;
+    if (tid == 0) { cfront = 0; cback = 0; }
     __syncthreads();  // also: the previous round's transpose is done (M reset, gbuf free)
+    PR_STAMP(3);
+#ifdef PR_RAST_PROFILE
+    ++rounds;
+#endif
     // ---- 1. scan + compaction + face registration
     int64_t f[kBwdEnt / kBwdThreads];
-    int pk[kBwdEnt / kBwdThreads];  // (pixel << 16) | k
+    int pk[kBwdEnt / kBwdThreads];  // (pixel << 10) | k
+    bool front[kBwdEnt / kBwdThreads];
 #pragma unroll
     for (int u = 0; u < kBwdEnt / kBwdThreads; ++u) {
       const int i = c0 + u * kBwdThreads + tid;
       f[u] = -1;
       pk[u] = 0;
+      front[u] = false;
       if (i < total) {
         int q = 0;  // the pixel: last q with pstart[q] <= i (binary search over TP entries)
 #pragma unroll
         for (int step = TP / 2; step > 0; step >>= 1)
           if (pstart[q + step] <= i) q += step;
         const int k = i - pstart[q], r = q / kBwdTile, c = q - r * kBwdTile;
-        pk[u] = (q << 16) | k;
-        f[u] = a.pix_to_face[tile_o + r * row_stride + c * K + k];
+        const int64_t o = tile_o + r * row_stride + c * K + k;
+        pk[u] = (q << 10) | k;
+        f[u] = a.pix_to_face[o];
+        if constexpr (EXACT) front[u] = a.grad_dists ? a.grad_dists[o] != 0.f : false;  // NaN: front
+        else front[u] = true;
       }
     }
 #pragma unroll
@@ -1786,44 +1879,70 @@ __global__ void __launch_bounds__(kBwdThreads) rast_bwd_kernel(PRRastArgs a, int
       const bool keep = f[u] >= 0;
       const uint64_t bal = __ballot(keep);
       if (bal == 0) continue;
-      int off = 0;
-      if (lane == 0) off = atomicAdd(&ccount, __popcll(bal));
-      off = __shfl(off, 0);
+      const uint64_t balf = __ballot(keep && front[u]), balb = bal & ~balf;
+      int offf = 0, offb = 0;
+      if (lane == 0) {
+        if (balf) offf = atomicAdd(&cfront, __popcll(balf));
+        if (balb) offb = atomicAdd(&cback, __popcll(balb));
+      }
+      offf = __shfl(offf, 0);
+      offb = __shfl(offb, 0);
       if (!keep) continue;
       const int fi = (int)f[u];
-      clist[off + __popcll(bal & ((1ull << lane) - 1ull))] = make_int2(pk[u], fi);
-      uint32_t h = ((uint32_t)fi * 2654435761u) & (kHash - 1);
+      uint32_t h = ((uint32_t)fi * 2654435761u) & (kHash - 1), hs = kBwdNoHash;
       for (int probe = 0; probe < 32; ++probe) {
         const int cur = atomicCAS(&hkey[h], -1, fi);
         if (cur == -1) {  // first slot of this face in the tile: assign its local index
           const int fl = atomicAdd(&nface, 1);
           hfl[h] = fl;
           if (fl < kBwdFaces) flist[fl] = fi;
+          hs = h;
           break;
         }
-        if (cur == fi) break;
+        if (cur == fi) { hs = h; break; }
         h = (h + 1) & (kHash - 1);
       }
+      // the round scans kBwdEnt slots, so the two groups never meet
+      const uint64_t below = (1ull << lane) - 1ull;
+      const int pos = front[u] ? offf + __popcll(balf & below) : kBwdEnt - 1 - (offb + __popcll(balb & below));
+      clist[pos] = ((uint32_t)pk[u] << 10) | hs;
     }
     __syncthreads();
-    // ---- 2. dense per-slot gradients
-    const int nv = ccount;
-    for (int j = tid; j < nv; j += kBwdThreads) {
-      const int2 e = clist[j];
-      const int pix = e.x >> 16, k = e.x & 0xffff, fi = e.y;
+    PR_STAMP(1);
+    // ---- 2. dense per-slot gradients: lanes [0, nfr) the front group, [nfr, nv) the back group
+    const int nfr = cfront, nv = nfr + cback;
+#pragma unroll
+    for (int u = 0; u < kBwdEnt / kBwdThreads; ++u) {
+      const int jj = u * kBwdThreads + tid;
+      if (jj >= nv) break;
+      const bool with_dist = jj < nfr;
+      const int j = with_dist ? jj : jj + (kBwdEnt - nv);
+      const uint32_t e = clist[j];
+      const int pix = e >> 20, k = (e >> 10) & 1023;
+      const uint32_t hs = e & 1023;
       const int r = pix >> 3, c = pix & 7;
       const int64_t o = tile_o + r * row_stride + c * K + k;
+      int fi, fl = kBwdFaces;  // no hash slot (overflow): global path
+      if (hs != kBwdNoHash) { fi = hkey[hs]; fl = hfl[hs]; }
+      else fi = (int)a.pix_to_face[o];
+#ifdef PR_RAST_PROFILE
+      {
+        const bool nz = a.grad_zbuf && a.grad_zbuf[o] != 0.f, nd = a.grad_dists && a.grad_dists[o] != 0.f;
+        const bool nb = a.grad_bary && (a.grad_bary[o * 3] != 0.f || a.grad_bary[o * 3 + 1] != 0.f ||
+                                        a.grad_bary[o * 3 + 2] != 0.f);
+        const uint64_t bz = __ballot(nz), bd = __ballot(nd), bb = __ballot(nb), bn = __ballot(!nz && !nd && !nb);
+        if (lane == __ffsll((unsigned long long)__ballot(true)) - 1) {  // one LDS add per wave and counter
+          atomicAdd(&pcount[0], __popcll(bz));
+          atomicAdd(&pcount[1], __popcll(bd));
+          atomicAdd(&pcount[2], __popcll(bb));
+          atomicAdd(&pcount[3], __popcll(bn));
+        }
+      }
+#endif
       const V2 p{pxs[c], pys[r]};
       float g[9];
-      slot_grad_any<EXACT>(a, p, a.face_verts + (int64_t)fi * 9, o, g);
-      uint32_t h = ((uint32_t)fi * 2654435761u) & (kHash - 1);
-      int fl = kBwdFaces;  // not found (hash overflow): global path
-      for (int probe = 0; probe < 32; ++probe) {
-        const int cur = hkey[h];
-        if (cur == fi) { fl = hfl[h]; break; }
-        if (cur == -1) break;
-        h = (h + 1) & (kHash - 1);
-      }
+      if constexpr (EXACT) slot_grad_exact(a, p, a.face_verts + (int64_t)fi * 9, o, g, !with_dist);
+      else slot_grad(a, p, a.face_verts + (int64_t)fi * 9, o, g);
       if (fl < kBwdFaces) {
 #pragma unroll
         for (int cc = 0; cc < 9; ++cc) gbuf[cc * kBwdEnt + j] = g[cc];
@@ -1834,13 +1953,17 @@ __global__ void __launch_bounds__(kBwdThreads) rast_bwd_kernel(PRRastArgs a, int
       }
     }
     __syncthreads();
-    // ---- 3. transpose: owner lanes sum their face's entries (and reset their M row)
-    if (tid < min(nface, kBwdFaces)) {
-      uint64_t* col = reinterpret_cast<uint64_t*>(M) + tid;
-      for (int q = 0; q < nrows * kBwdTile; q += 4) {
-        const uint64_t four = col[(q >> 2) * kBwdFaces];
+    PR_STAMP(2);
+    // ---- 3. transpose: owner lanes sum their face's entries (and reset their M quads)
+    if (own_fl < min(nface, kBwdFaces)) {
+      uint64_t* col = reinterpret_cast<uint64_t*>(M) + own_fl;
+      float acc[9];
+#pragma unroll
+      for (int cc = 0; cc < 9; ++cc) acc[cc] = sums[cc * kBwdThreads + tid];
+      for (int q4 = own_part; q4 < nrows * (kBwdTile / 4); q4 += kBwdSplit) {
+        const uint64_t four = col[q4 * kBwdFaces];
         if (four == ~0ull) continue;
-        col[(q >> 2) * kBwdFaces] = ~0ull;
+        col[q4 * kBwdFaces] = ~0ull;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
           const uint32_t jj = (uint32_t)(four >> (16 * t)) & 0xffffu;
@@ -1849,20 +1972,27 @@ __global__ void __launch_bounds__(kBwdThreads) rast_bwd_kernel(PRRastArgs a, int
           for (int cc = 0; cc < 9; ++cc) acc[cc] += gbuf[cc * kBwdEnt + jj];
         }
       }
+#pragma unroll
+      for (int cc = 0; cc < 9; ++cc) sums[cc * kBwdThreads + tid] = acc[cc];
     }
   }
   __syncthreads();
-  // ---- 4. flush: sums to LDS, then lane-contiguous over (face, component)
+  PR_STAMP(3);
+  // ---- 4. flush: lane-contiguous over (face, component), the owners' partial sums of a face
+  //         added in their fixed order
   const int nf = min(nface, kBwdFaces);
-  if (tid < nf) {
-#pragma unroll
-    for (int cc = 0; cc < 9; ++cc) gbuf[tid * 9 + cc] = acc[cc];
-  }
-  __syncthreads();
   for (int i = tid; i < nf * 9; i += kBwdThreads) {
     const int fl = i / 9, cc = i - fl * 9;
-    atomicAdd(&a.grad_face_verts[(int64_t)flist[fl] * 9 + cc], gbuf[i]);
+    float s = sums[cc * kBwdThreads + fl];
+#pragma unroll
+    for (int part = 1; part < kBwdSplit; ++part) s += sums[cc * kBwdThreads + part * kBwdFaces + fl];
+    atomicAdd(&a.grad_face_verts[(int64_t)flist[fl] * 9 + cc], s);
   }
+#ifdef PR_RAST_PROFILE
+  __syncthreads();
+  PR_STAMP(4);
+  if (tid == 0) bwd_prof_record(rt0, stamp, tile_x, row0 / tile_rows, total, rounds, nface, pcount);
+#endif
 }
 
 // ------------------------------------------------------------ interpolation
@@ -2105,6 +2235,11 @@ using namespace pr;
 extern "C" int pr_rast_prof_dump(void* dst, size_t bytes) {
   return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_rast_prof), bytes < sizeof(g_rast_prof) ? bytes : sizeof(g_rast_prof),
                              0, hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
+}
+extern "C" int pr_rast_bwd_prof_dump(void* dst, size_t bytes) {
+  return hipMemcpyFromSymbol(dst, HIP_SYMBOL(g_rast_bwd_prof),
+                             bytes < sizeof(g_rast_bwd_prof) ? bytes : sizeof(g_rast_bwd_prof), 0,
+                             hipMemcpyDeviceToHost) == hipSuccess ? 0 : -1;
 }
 #endif
 
