@@ -210,7 +210,14 @@ typedef struct PRBlendGeometry {
   int32_t nch;         /* backward: lanes that share an entry's sample sum in B6 (0 for the forward) */
   int32_t b2_regs;     /* backward: B2 keeps its chunks in registers (else LDS; 0 for the forward) */
   int32_t interleaved; /* interleaved pixel blocks (else consecutive) */
+  int32_t order;       /* block order of the static grid: PR_BLEND_ORDER_LINEAR / _CENTRE_OUT / _ROTATED */
 } PRBlendGeometry;
+
+/* which pixel block the workgroup of a dispatch index takes (pr_blend_block_order) */
+#define PR_BLEND_ORDER_LINEAR 0
+#define PR_BLEND_ORDER_CENTRE_OUT 1 /* centre-out within each image; blocks must tile images */
+#define PR_BLEND_ORDER_ROTATED 2    /* every block row rotated in itself, so that the 8 XCDs and their CUs */
+                                    /* each meet every column band; blocks must tile image rows            */
 
 typedef struct PRHeavisideArgs {
   int32_t N, H, W, K, Sr, sample_offset_r, noise_mode;
@@ -650,6 +657,12 @@ int pr_blend_bwd(const PRBlendBwdArgs* args, void* stream);
  * pr_blend_bwd (bwd != 0) would launch for `p` under the current PR_BLEND_* environment; reads the
  * shape, sample and flag fields of `p` only (tests assert the path a case takes). */
 int pr_blend_geometry(const PRBlendParams* p, int bwd, PRBlendGeometry* out);
+/* Host only, no launch: blocks[i] = the pixel block that dispatch index i of a static grid of PB-pixel
+ * blocks over N images of H x W takes under `order` (PR_BLEND_ORDER_*), the function the kernels
+ * call; nblocks must be ceil(N H W / PB).  An order the shape cannot take falls back to linear;
+ * *taken (nullable) is the order in effect. */
+int pr_blend_block_order(int32_t N, int32_t H, int32_t W, int32_t PB, int32_t order, int32_t* blocks,
+                         int64_t nblocks, int32_t* taken);
 
 int pr_heaviside_fwd(const PRHeavisideArgs* args, void* stream);
 size_t pr_heaviside_bwd_workspace_size(const PRHeavisideArgs* args);

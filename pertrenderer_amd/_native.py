@@ -68,7 +68,11 @@ class PRBlendBwdArgs(C.Structure):
 class PRBlendGeometry(C.Structure):
     _fields_ = [("PB", C.c_int32), ("cap", C.c_int32), ("lds_bytes", C.c_int32), ("lpp", C.c_int32),
                 ("multi", C.c_int32), ("NC", C.c_int32), ("nch", C.c_int32), ("b2_regs", C.c_int32),
-                ("interleaved", C.c_int32)]
+                ("interleaved", C.c_int32), ("order", C.c_int32)]
+
+
+# PRBlendGeometry.order / pr_blend_block_order: which pixel block a dispatch index takes
+BLEND_ORDER_LINEAR, BLEND_ORDER_CENTRE_OUT, BLEND_ORDER_ROTATED = 0, 1, 2
 
 
 class PRHeavisideArgs(C.Structure):
@@ -189,6 +193,8 @@ EXPORTS = {
     "pr_blend_bwd_workspace_size": (C.c_size_t, [C.POINTER(PRBlendBwdArgs)]),
     "pr_blend_bwd": (C.c_int, [C.POINTER(PRBlendBwdArgs), _vp]),
     "pr_blend_geometry": (C.c_int, [C.POINTER(PRBlendParams), C.c_int, C.POINTER(PRBlendGeometry)]),
+    "pr_blend_block_order": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _vp, C.c_int64,
+                                       C.POINTER(C.c_int32)]),
     "pr_heaviside_fwd": (C.c_int, [C.POINTER(PRHeavisideArgs), _vp]),
     "pr_heaviside_bwd_workspace_size": (C.c_size_t, [C.POINTER(PRHeavisideArgs)]),
     "pr_heaviside_bwd": (C.c_int, [C.POINTER(PRHeavisideArgs), _vp]),
@@ -260,6 +266,18 @@ def check(code, what):
     if code != 0:
         msg = load().pr_last_error().decode(errors="replace")
         raise NativeError(f"{what} failed ({code}): {msg}")
+
+
+def blend_block_order(N, H, W, PB, order):
+    """(blocks, taken): the pixel block of every dispatch index of a static blend grid under
+    `order` (BLEND_ORDER_*) as an int32 array, and the order in effect (linear where the shape
+    cannot take the one asked for).  Host only: pr_blend_block_order."""
+    import numpy as np
+    blocks = np.empty((N * H * W + PB - 1) // PB if min(N, H, W, PB) > 0 else 1, dtype=np.int32)
+    taken = C.c_int32(-1)
+    check(load().pr_blend_block_order(N, H, W, PB, order, blocks.ctypes.data, blocks.size, C.byref(taken)),
+          "pr_blend_block_order")
+    return blocks, taken.value
 
 
 def ptr(t):

@@ -38,21 +38,23 @@ constexpr float kNegInf = -__builtin_inff();
 constexpr float kEpsMaxBM = 5.8f;               // > sqrt(-2 ln 2^-24) = 5.7683
 
 #ifdef PR_BLEND_PROFILE
-// diagnostic build: per block [start, end (100 MHz), phases (shader clock) x8, hw id, flag];
-// fwd blocks at [0, 1<<16), bwd blocks at [1<<16, 2<<16)
+// diagnostic build: per block [start, end (100 MHz), phases (shader clock) x8, HW_ID | XCC_ID << 32,
+// 1 | entries << 8 | dispatch index << 32]; fwd blocks at [0, 1<<16), bwd blocks at [1<<16, 2<<16)
 constexpr unsigned kBProfBlocks = 1 << 16;
 constexpr int kBProfRec = 12;
 __device__ long long g_blend_prof[2 * kBProfBlocks * kBProfRec];
 #define PR_BPROF_DECL long long bst_[8] = {0, 0, 0, 0, 0, 0, 0, 0}, bt_ = __builtin_amdgcn_s_memtime(), \
                       brt_ = __builtin_amdgcn_s_memrealtime()
-#define PR_BPROF_DUMP(which, rec)                                                              \
+#define PR_BPROF_DUMP(which, rec, ent)                                                         \
   if (threadIdx.x == 0 && (rec) < kBProfBlocks) {                                              \
-    unsigned hw_;                                                                              \
+    unsigned hw_, xcc_;                                                                        \
     asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_));                          \
+    asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xcc_));                        \
     long long* r_ = g_blend_prof + ((size_t)(which) * kBProfBlocks + (rec)) * kBProfRec;       \
     r_[0] = brt_; r_[1] = (long long)__builtin_amdgcn_s_memrealtime();                          \
     for (int i_ = 0; i_ < 8; ++i_) r_[2 + i_] = bst_[i_];                                       \
-    r_[10] = hw_; r_[11] = 1;                                                                  \
+    r_[10] = (long long)hw_ | (long long)(xcc_ & 0xf) << 32;                                   \
+    r_[11] = 1 | (long long)(ent) << 8 | (long long)blockIdx.x << 32;                          \
   }
 #define PR_BSTAMP(i) (bst_[i] += __builtin_amdgcn_s_memtime() - bt_, bt_ = __builtin_amdgcn_s_memtime())
 #else
@@ -76,6 +78,8 @@ struct Geo {
   int qK, rK, qK1, rK1, qS, rS;  // 256 / {K, K+1, Sa} and remainders
   int lpp, lsh;                  // lanes per pixel in the pixel phases (256 / PB, 8..64) and log2
   int bpi;                       // blocks per image for the centre-out block order (0: linear)
+  int rot, rotC, rotY;           // rotated block order (rotated_block): blocks per image (0: off),
+                                 // blocks per image row, block rows per 256-block dealing cycle
   int tail;                      // backward: joint masked-tail draw allowed (PR_BLEND_TAIL=0: off)
   int empty;                     // empty-block shortcut allowed (PR_BLEND_EMPTY=0: off)
   int cap;                       // LDS entry records per workgroup (>= K + 1)
@@ -153,12 +157,64 @@ PR_DEV bool last_arrival(int32_t* sync, int nblk, int* flag, bool rel) {
   return last;
 }
 
-// pixel block of this workgroup: centre-out within each image when blocks tile images
-PR_DEV int64_t pixel_block(const Geo& g) {
-  if (g.bpi == 0) return blockIdx.x;
-  const int64_t n = blockIdx.x / g.bpi;
-  return n * g.bpi + centre_out((int)(blockIdx.x - n * g.bpi), g.bpi);
+// Block orders of the static grid: which pixel block the workgroup of a dispatch index takes
+// (PR_BLEND_ORDER, PRBlendGeometry.order).  Outputs do not depend on it: partials are indexed by
+// pixel block, Philox counters by physical pixel.
+constexpr int kOrderLinear = 0, kOrderCentreOut = 1, kOrderRotated = 2;
+
+// Rotated order, for blocks that tile image rows (C >= 2 blocks per row): dispatch index i of an
+// image is row r = i / C, column c = i % C, and takes the block of that row at column
+// (c + r + 5 (r / Y)) % C, Y = 256 / C rows per dealing cycle.  Consecutive workgroups go to the 8
+// XCDs in turn and within an XCD to its 32 CUs in turn, so in linear order XCD x holds the column
+// bands x, x + 8, ... of every row and a CU one column of every Y-th row: an object in the frame
+// loads the XCDs by up to 1.35x / 1.58x the mean (16 / 8 blocks per row on the bench frame) and
+// leaves CUs idle.  The step of one column per row moves a band through all XCDs; the 5 more per
+// cycle move it through an XCD's CUs (a plain c + r repeats with the cycle).  A bijection of each
+// image's blocks for any C, Y >= 1: every row is rotated in itself.
+PR_HD int rotated_block(int i, int C, int Y) {
+  const int r = i / C, c = i - r * C;
+  return r * C + (int)(((int64_t)c + r + 5 * (int64_t)(r / Y)) % C);
 }
+
+struct BlockOrder {
+  int kind;           // the order taken: kOrderLinear / kOrderCentreOut / kOrderRotated
+  int bpi;            // centre-out: blocks per image (else 0)
+  int rot, rotC, rotY;  // rotated: blocks per image (else 0), blocks per row, rows per dealing cycle
+};
+
+// The order a grid of PB-pixel blocks over H x W images takes when `want` is asked for: centre-out
+// needs blocks that tile images, rotated blocks that tile image rows (whole-row blocks, W % PB != 0
+// with PB % W == 0, have one column: nothing to rotate); otherwise linear.
+PR_HD BlockOrder block_order(int H, int W, int PB, int want) {
+  BlockOrder o{kOrderLinear, 0, 0, 0, 0};
+  const int64_t HW = (int64_t)H * W;
+  if (want == kOrderCentreOut && HW % PB == 0) {
+    o.kind = kOrderCentreOut;
+    o.bpi = (int)(HW / PB);
+  } else if (want == kOrderRotated && W % PB == 0 && W / PB >= 2) {
+    o.kind = kOrderRotated;
+    o.rot = (int)(HW / PB);
+    o.rotC = W / PB;
+    o.rotY = o.rotC < 256 ? 256 / o.rotC : 1;
+  }
+  return o;
+}
+
+// pixel block of dispatch index i (the one definition: the kernels' and pr_blend_block_order's)
+PR_HD int64_t ordered_block(unsigned i, int bpi, int rot, int rotC, int rotY) {
+  if (rot) {
+    const unsigned n = i / (unsigned)rot;
+    return (int64_t)n * rot + rotated_block((int)(i - n * rot), rotC, rotY);
+  }
+  if (bpi) {
+    const unsigned n = i / (unsigned)bpi;
+    return (int64_t)n * bpi + centre_out((int)(i - n * bpi), bpi);
+  }
+  return i;
+}
+
+// pixel block of this workgroup
+PR_DEV int64_t pixel_block(const Geo& g) { return ordered_block(blockIdx.x, g.bpi, g.rot, g.rotC, g.rotY); }
 
 // Pixel j of pixel block blk.  Consecutive (pm = 0): blk * PB + j.  Interleaved (pm = 1, blocks
 // tiling images): within its image, block b takes pixel t = j * NBI + b (NBI = HW / PB blocks per
@@ -965,7 +1021,7 @@ PR_DEV void fwd_tile(const FwdK& a, const Geo& g, const int NC0, const Sc& sc, c
   PR_BSTAMP(5);
   }  // passes
 #ifdef PR_BLEND_PROFILE
-  PR_BPROF_DUMP(0, rec);
+  PR_BPROF_DUMP(0, rec, EA[bnpix]);
 #endif
 }
 
@@ -1588,7 +1644,7 @@ PR_DEV void bwd_tile(const BwdK& a, const Geo& g, const Sc& sc, float* partials,
   if (tid < 4) put_partial(a, partials + pidx * 4 + tid, (RED[tid] + RED[4 + tid]) + (RED[8 + tid] + RED[12 + tid]));
 #ifdef PR_BLEND_PROFILE
   PR_BSTAMP(7);
-  PR_BPROF_DUMP(1, pidx);
+  PR_BPROF_DUMP(1, pidx, EA[bnpix]);
 #endif
   __syncthreads();  // (SEG: the next segment rewrites RED)
 }
@@ -1965,6 +2021,20 @@ void launch_bwd(const BwdK& a, Geo geo, hipStream_t st, size_t lds, int nblk, fl
   ktimer_mark(1, "blend_bwd_kernel", st);
 }
 
+// PR_BLEND_ORDER unset: the rotated order for both kernels (profiles/blend_order/README.md: cfg 2
+// blend_bwd 72.1 -> 67.0 us with the XCDs' entries at 1.00x the mean instead of 1.35x, the forward
+// equal to centre-out on the centred bench frame; batches' forward cfg 3 +3.4 %, cfg 4 +7.4 %
+// frames/s over linear, where centre-out lost).  The interleaved backward has no order to choose.
+int default_order() { return 4 | 8; }
+
+// The segment plan keeps its own ranking of the blocks, linear or centre-out: PR_BLEND_ORDER's
+// centre-out bits, unset the forward of a single frame
+int plan_bpi(const PRBlendParams& p, int PB, bool bwd) {
+  const char* env = getenv("PR_BLEND_ORDER");
+  const int order = env && atoi(env) >= 0 ? atoi(env) : (p.N == 1 ? 1 : 0);
+  return block_order(p.H, p.W, PB, (order >> (bwd ? 1 : 0) & 1) ? kOrderCentreOut : kOrderLinear).bpi;
+}
+
 Geo make_geo(const PRBlendParams& p, int PB, bool bwd) {
   Geo g;
   g.P = (int64_t)p.N * p.H * p.W;
@@ -1989,12 +2059,19 @@ Geo make_geo(const PRBlendParams& p, int PB, bool bwd) {
   while (lpp > 8 && lpp * PB > kThreads) lpp >>= 1;
   g.lpp = lpp;
   g.lsh = 31 - __builtin_clz(g.lpp);
-  // centre-out block order (PR_BLEND_ORDER bit 0: forward, bit 1: backward; 0 = linear).
-  // Default: the forward of a single frame only (cfg 2); on batches linear order is faster
-  // (cfg 4 blend_fwd 5.16 -> 4.72 ms, cfg 3 equal), and the backward is linear everywhere.
-  static const int order_env = getenv("PR_BLEND_ORDER") ? atoi(getenv("PR_BLEND_ORDER")) : -1;
-  const int order = order_env >= 0 ? order_env : (p.N == 1 ? 1 : 0);
-  g.bpi = (order >> (bwd ? 1 : 0) & 1) && g.HW % PB == 0 ? g.HW / PB : 0;
+  // block order (block_order): PR_BLEND_ORDER bit 0 / 1: centre-out forward / backward, bit 2 / 3:
+  // rotated forward / backward (wins over centre-out), 0 = linear; read per call: tests compare
+  // orders in one process.  Default: default_order().
+  const char* order_env = getenv("PR_BLEND_ORDER");
+  const int order = order_env && atoi(order_env) >= 0 ? atoi(order_env) : default_order();
+  const int sh = bwd ? 1 : 0;
+  const BlockOrder bo = block_order(p.H, p.W, PB, (order >> (2 + sh) & 1)   ? kOrderRotated
+                                                  : (order >> sh & 1) ? kOrderCentreOut
+                                                                      : kOrderLinear);
+  g.bpi = bo.bpi;
+  g.rot = bo.rot;
+  g.rotC = bo.rotC;
+  g.rotY = bo.rotY;
   static const int tail = getenv("PR_BLEND_TAIL") ? atoi(getenv("PR_BLEND_TAIL")) : 1;
   g.tail = tail;
   const char* empty = getenv("PR_BLEND_EMPTY");  // read per call: tests compare both paths in one process
@@ -2007,14 +2084,18 @@ Geo make_geo(const PRBlendParams& p, int PB, bool bwd) {
   // one-frame grids keep consecutive blocks, whose empty-block shortcut
   // frees half the grid at once (interleaved, every block carries work and the forward's 2048
   // blocks outnumber the 1792 resident: cfg 2 3197 -> 3060, eval 3460 -> 3205;
-  // profiles/r4_experiments.txt).  PR_BLEND_INTERLEAVE=0|1 forces it (read per call: tests compare
+  // profiles/r4_experiments.txt).  Those figures were taken against consecutive blocks in linear
+  // order; against the rotated order (profiles/blend_order/README.md) the interleaved backward is
+  // equal at cfg 3 (6834 / 6870 vs 6852 / 6904 frames/s) and behind at cfg 4 (1202 / 1203 vs 1281 /
+  // 1284), ahead of linear at both (6413 / 6453, 1120 / 1124): the threshold is still to re-decide.
+  // PR_BLEND_INTERLEAVE=0|1 forces it (read per call: tests compare
   // both layouts in one process); the segment plan turns it off.
   const char* il = getenv("PR_BLEND_INTERLEAVE");
   g.pm = (il ? atoi(il) != 0 : bwd && g.P / PB > 8192) && PB > 1 && g.HW % PB == 0;
   g.pmNBI = g.pm ? g.HW / PB : 1;
   g.pmW = p.W;
   g.pmA = g.pm && g.pmNBI % p.W == 0 ? ((int)(0.6180339887 * p.W) | 1) % p.W : 0;
-  if (g.pm) g.bpi = 0;  // balanced blocks: no dispatch order to choose
+  if (g.pm) g.bpi = g.rot = 0;  // balanced blocks: no dispatch order to choose
   // fused scalar reduction's arrivals: relaxed (default) or acq_rel (PR_BLEND_SYNC_ORDER=release;
   // read per call: tests compare both in one process)
   const char* so = getenv("PR_BLEND_SYNC_ORDER");
@@ -2063,7 +2144,7 @@ PlanCfg plan_cfg(const PRBlendParams& p, const int32_t* pcnt) {
     c.q.lo[w] = lo;
     c.q.hi[w] = hi;
     c.q.X[w] = (int)((P * KP1 + hi - 1) / hi);  // a dense frame's parts at E = hi
-    c.q.bpi[w] = g.bpi;
+    c.q.bpi[w] = g.pm ? 0 : plan_bpi(p, sh.PB, w == 1);
     c.q.T[w] = (int)((P + sh.PB - 1) / sh.PB);
     int ls = g.lsh;
     while (ls < 6 && (2 << ls) <= l_env[w]) ++ls;
@@ -2244,6 +2325,22 @@ extern "C" int pr_blend_geometry(const PRBlendParams* p, int bwd, PRBlendGeometr
   out->nch = bwd ? b6_lane_split(agg_num_groups(*p)) : 0;
   out->b2_regs = bwd ? b2_in_regs(ln.multi, ln.geo.KP1, ln.geo.lpp) : 0;
   out->interleaved = ln.geo.pm;
+  out->order = ln.geo.rot ? kOrderRotated : ln.geo.bpi ? kOrderCentreOut : kOrderLinear;
+  return PR_OK;
+}
+
+extern "C" int pr_blend_block_order(int32_t N, int32_t H, int32_t W, int32_t PB, int32_t order, int32_t* blocks,
+                                    int64_t nblocks, int32_t* taken) {
+  if (N <= 0 || H <= 0 || W <= 0 || PB <= 0) return set_error(PR_ERR_ARG, "blend_block_order: bad shape");
+  if (order != kOrderLinear && order != kOrderCentreOut && order != kOrderRotated)
+    return set_error(PR_ERR_ARG, "blend_block_order: unknown order");
+  if ((int64_t)H * W >= (int64_t(1) << 31)) return set_error(PR_ERR_ARG, "blend_block_order: image too large");
+  const int64_t nb = ((int64_t)N * H * W + PB - 1) / PB;
+  if (nb >= (int64_t(1) << 31)) return set_error(PR_ERR_ARG, "blend_block_order: too many blocks");
+  if (!blocks || nblocks != nb) return set_error(PR_ERR_ARG, "blend_block_order: blocks must hold ceil(N H W / PB) entries");
+  const BlockOrder o = block_order(H, W, PB, order);
+  for (int64_t i = 0; i < nb; ++i) blocks[i] = (int32_t)ordered_block((unsigned)i, o.bpi, o.rot, o.rotC, o.rotY);
+  if (taken) *taken = o.kind;
   return PR_OK;
 }
 

@@ -107,7 +107,7 @@ PR_DEV uint64_t mix64(uint64_t z) {
 // pr_seed_advance's update of a device key base (DeviceSeed.advance)
 PR_DEV uint64_t seed_next(uint64_t s) { return mix64(s + 0x9E3779B97F4A7C15ull); }
 
-PR_DEV int centre_out(int k, int n) { return (k & 1) ? n / 2 - 1 - (k >> 1) : n / 2 + (k >> 1); }
+PR_HD int centre_out(int k, int n) { return (k & 1) ? n / 2 - 1 - (k >> 1) : n / 2 + (k >> 1); }
 
 // --------------------------------------------------------------------- math
 PR_DEV float heaviside1(float x) { return x >= 0.f ? 1.f : 0.f; }  // torch.heaviside(x, 1)
