@@ -88,7 +88,17 @@ struct Geo {
   int plan_fwd_list, plan_bwd_list;  // segment plan: int offsets of the two segment lists
   int pm, pmNBI, pmW, pmA;           // interleaved pixel blocks (block_pixel; pm = 0: consecutive)
   int sync_rel;                      // fused scalar reduction: acq_rel arrivals (last_arrival)
+  int chain;                         // PR_BLEND_CHAIN: kChainPrio | kChainGatherOnce
 };
+
+// PR_BLEND_CHAIN, one bit per measure that shortens a block's chain of dependent stages (read per
+// call; no output depends on either, profiles/blend_chain/README.md):
+//   kChainPrio        forward: the waves of blocks holding many entries raise their priority;
+//   kChainGatherOnce  backward from dists with vertex colours, single pass on the static grid (its
+//                     own kernel instance, ONCE; every other launch keeps its kernel): B2 resolves
+//                     a won slot's pix_to_face -> faces -> vert_colors gather once, one thread
+//                     per entry, and finishes d bary (and d vert_colors) there; B8 gathers nothing.
+constexpr int kChainPrio = 1, kChainGatherOnce = 2;
 
 // a value every lane holds alike (read from LDS: a vector register) into a scalar register
 PR_DEV int uni(int x) { return __builtin_amdgcn_readfirstlane(x); }
@@ -693,6 +703,13 @@ PR_DEV void fwd_tile(const FwdK& a, const Geo& g, const int NC0, const Sc& sc, c
   if (tid < 64) block_entries(g, blk, pcnt, bnpix, K, pcnt != nullptr, CAP, PB, CL, CP, EA, PS, GPX, SEG ? g.seg : 0);
   __syncthreads();
   const float gal = sc.gamma / sc.alpha;
+  // critical-path priority (kChainPrio): the forward runs in one generation and ends with its
+  // heaviest block, so blocks at >= 0.8 / 0.6 of a full block's entries go first on their SIMDs
+  if (g.chain & kChainPrio) {
+    const int tot = uni(EA[bnpix]), full = PB * KP1;
+    if (5 * tot >= 4 * full) __builtin_amdgcn_s_setprio(2);
+    else if (5 * tot >= 3 * full) __builtin_amdgcn_s_setprio(1);
+  }
   // ---- empty block (no pixel has a valid slot: only background entries): every sample's
   //      argmax is the background, W_bg = Sa / Sa = 1, alpha = 1 - (empty product) = 0; the
   //      same values the phases below would produce, without them
@@ -771,6 +788,10 @@ PR_DEV void fwd_tile(const FwdK& a, const Geo& g, const int NC0, const Sc& sc, c
           }
         }
       }
+#ifdef PR_BLEND_PROF_SPLIT_1A  // diagnostic: 1a's load rounds to slot 6, its records and appends to slot 1
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      PR_BSTAMP(6);
+#endif
 #pragma unroll
       for (int u = 0; u < kU; ++u) {
         const int pl = bt.pl[u], k = bt.k[u], li = i0 + u * kThreads;  // entry index
@@ -1069,7 +1090,7 @@ PR_HD bool b2_in_regs(bool multi, int KP1, int lpp) { return !multi && KP1 <= kB
 //
 // One pixel block of the backward: all passes (static grid) or segment part `part` (SEG); its
 // scalar partials go to partials[4 pidx .. 4 pidx + 4).
-template <int NOISE, bool RAST, int CM, bool MULTI, bool SEG>
+template <int NOISE, bool RAST, int CM, bool MULTI, bool SEG, bool ONCE = false>
 PR_DEV void bwd_tile(const BwdK& a, const Geo& g, const Sc& sc, float* partials, const int64_t blk,
                      const int part, const int64_t pidx) {
   extern __shared__ float smem[];
@@ -1387,7 +1408,7 @@ PR_DEV void bwd_tile(const BwdK& a, const Geo& g, const Sc& sc, float* partials,
       // dW = g_rgb . colour of the slot entries B5 reads (a win, or j0): the colour is
       // interpolated from the vertex colours here (CM 2), or read from the forward's colours of
       // exactly those slots (CM 4: PR_BLEND_PHONG's sparse colours), once per such entry
-      if (act) {
+      if (act && !ONCE) {
         const float* gi = PX + pl * 12 + 8;
         for (int e = l; e < c; e += lpp) {
           const int cnt = CN[e0 + e];
@@ -1396,6 +1417,53 @@ PR_DEV void bwd_tile(const BwdK& a, const Geo& g, const Sc& sc, float* partials,
           slot_color<CM>(a, (int64_t)gpx[pl] * K + e, cc);
           DW[e0 + e] = (gi[0] * cc[0] + gi[1] * cc[1]) + gi[2] * cc[2];
         }
+      }
+    }
+  }
+  // kChainGatherOnce (vertex colours): the same entries, one thread per entry instead of the
+  // pixel's lanes (a pass has few such entries: each thread runs at most one pix_to_face -> faces
+  // -> vert_colors chain, all of them side by side, where a lane ran its pixel's in series), and a
+  // won slot's gather also finishes what B8 gathered again for: d bary and d vert_colors
+  // (slot_color's and B8's operations in their order; B8 then skips the slot).  j0 comes from PX.
+  if constexpr (ONCE) {
+    __syncthreads();
+    for (int li = tid; li < nent; li += kThreads) {
+      const int pl = OWN[li], e = li - (ea[pl] - eb);
+      if (e >= cl[pl]) continue;  // the background entry
+      const int cnt = CN[li];
+      if (cnt == 0 && e != (int)PX[pl * 12 + 3]) continue;
+      const float* gi = PX + pl * 12 + 8;
+      const int64_t gs = (int64_t)gpx[pl] * K + e;
+      const int64_t f = a.pix_to_face[gs];
+      float cc[3] = {0.f, 0.f, 0.f}, gb[3] = {0.f, 0.f, 0.f};
+      if (f >= 0) {
+        const float bw[3] = {a.bary[gs * 3], a.bary[gs * 3 + 1], a.bary[gs * 3 + 2]};
+        const int64_t v[3] = {a.faces[f * 3], a.faces[f * 3 + 1], a.faces[f * 3 + 2]};
+        float vc[3][3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i)
+#pragma unroll
+          for (int d = 0; d < 3; ++d) vc[i][d] = a.vert_colors[v[i] * 3 + d];
+#pragma unroll
+        for (int d = 0; d < 3; ++d) cc[d] = (bw[0] * vc[0][d] + bw[1] * vc[1][d]) + bw[2] * vc[2][d];
+        if (cnt != 0 && (!pcnt || e < cpv[pl])) {  // (B8's mask of the slot)
+          const float w = (float)cnt / (float)Sa;
+          const float dc[3] = {w * gi[0], w * gi[1], w * gi[2]};
+#pragma unroll
+          for (int d = 0; d < 3; ++d) {
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+              gb[i] += dc[d] * vc[i][d];
+              if (a.grad_vert_colors && dc[d] != 0.f) atomicAdd(&a.grad_vert_colors[v[i] * 3 + d], bw[i] * dc[d]);
+            }
+          }
+        }
+      }
+      DW[li] = (gi[0] * cc[0] + gi[1] * cc[1]) + gi[2] * cc[2];
+      if (cnt != 0) {
+        a.grad_bary[gs * 3] = gb[0];
+        a.grad_bary[gs * 3 + 1] = gb[1];
+        a.grad_bary[gs * 3 + 2] = gb[2];
       }
     }
   }
@@ -1575,6 +1643,7 @@ PR_DEV void bwd_tile(const BwdK& a, const Geo& g, const Sc& sc, float* partials,
     } else if constexpr (CM == 2) {
       // d colour = w * g_rgb, pushed through the interpolation (interp_bwd_kernel's order)
       const int cnt = CN[li];
+      if (ONCE && cnt != 0) continue;  // B2 wrote this slot's d bary
       float gb[3] = {0.f, 0.f, 0.f};
       const int64_t f = (cnt != 0 && m) ? (pcnt ? a.pix_to_face[gs] : fk) : -1;
       if (f >= 0) {
@@ -1700,12 +1769,12 @@ PR_DEV void finalize_scalars(const float* partials, int nblk, const PRBlendParam
   }
 }
 
-template <int NOISE, bool RAST, int CM, bool MULTI, bool SEG>
+template <int NOISE, bool RAST, int CM, bool MULTI, bool SEG, bool ONCE = false>
 __global__ void __launch_bounds__(kThreads, MULTI ? 6 : PR_BLEND_BWD_WPE) blend_bwd_kernel(BwdK a, Geo g, float* partials) {
   int nblk = (int)gridDim.x;
   if constexpr (!SEG) {
     const int64_t blk = pixel_block(g);
-    bwd_tile<NOISE, RAST, CM, MULTI, false>(a, g, resolve(a.p), partials, blk, -1, blk);
+    bwd_tile<NOISE, RAST, CM, MULTI, false, ONCE>(a, g, resolve(a.p), partials, blk, -1, blk);
   } else {
     const int32_t* plan = a.plan;
     const int si = blockIdx.x;
@@ -2012,7 +2081,15 @@ void launch_bwd(const BwdK& a, Geo geo, hipStream_t st, size_t lds, int nblk, fl
   ktimer_mark(0, "blend_bwd_kernel", st);
   if (cm == 4) {  // (RAST only, static grid: pr_blend_bwd checks)
     if constexpr (!SEG) launch_grid(blend_bwd_kernel<NOISE, true, 4, MULTI, false>, nblk, lds, st, a, geo, part);
-  } else if (rast && cm == 2) launch_grid(blend_bwd_kernel<NOISE, true, 2, MULTI, SEG>, nblk, lds, st, a, geo, part);
+  } else if (rast && cm == 2) {
+    // ONCE: kChainGatherOnce's instance (static grid, single pass); every other launch keeps its kernel
+    if constexpr (!MULTI && !SEG) {
+      if (geo.chain & kChainGatherOnce) launch_grid(blend_bwd_kernel<NOISE, true, 2, false, false, true>, nblk, lds, st, a, geo, part);
+      else launch_grid(blend_bwd_kernel<NOISE, true, 2, false, false>, nblk, lds, st, a, geo, part);
+    } else {
+      launch_grid(blend_bwd_kernel<NOISE, true, 2, MULTI, SEG>, nblk, lds, st, a, geo, part);
+    }
+  }
   else if (rast && cm == 1) launch_grid(blend_bwd_kernel<NOISE, true, 1, MULTI, SEG>, nblk, lds, st, a, geo, part);
   else if (rast) launch_grid(blend_bwd_kernel<NOISE, true, 0, MULTI, SEG>, nblk, lds, st, a, geo, part);
   else if (cm == 1) launch_grid(blend_bwd_kernel<NOISE, false, 1, MULTI, SEG>, nblk, lds, st, a, geo, part);
@@ -2026,6 +2103,9 @@ void launch_bwd(const BwdK& a, Geo geo, hipStream_t st, size_t lds, int nblk, fl
 // equal to centre-out on the centred bench frame; batches' forward cfg 3 +3.4 %, cfg 4 +7.4 %
 // frames/s over linear, where centre-out lost).  The interleaved backward has no order to choose.
 int default_order() { return 4 | 8; }
+
+// PR_BLEND_CHAIN unset (profiles/blend_chain/README.md)
+int default_chain() { return kChainPrio | kChainGatherOnce; }
 
 // The segment plan keeps its own ranking of the blocks, linear or centre-out: PR_BLEND_ORDER's
 // centre-out bits, unset the forward of a single frame
@@ -2100,6 +2180,9 @@ Geo make_geo(const PRBlendParams& p, int PB, bool bwd) {
   // read per call: tests compare both in one process)
   const char* so = getenv("PR_BLEND_SYNC_ORDER");
   g.sync_rel = so && so[0] == 'r';
+  // (read per call: tests compare the bits in one process)
+  const char* ch = getenv("PR_BLEND_CHAIN");
+  g.chain = ch && atoi(ch) >= 0 ? atoi(ch) : default_chain();
   return g;
 }
 

@@ -4,6 +4,9 @@
     PR_NATIVE_LIB=pertrenderer_amd/libpertrender_prof.so python tools/blend_prof.py
 Forward phases: setup / slots / MC rast / pixel / MC argmax / output.  Backward: setup / B1 / B2 /
 B5 / B6 / B7 / B8 / reduction.  Phases are summed over a block's passes.
+--split: the variant was also built with -D PR_BLEND_PROF_SPLIT_B2 -D PR_BLEND_PROF_SPLIT_1A: the
+forward's "slots" is then 1a's records and queue appends and "1a_load" its load round(s), the
+backward's "B2" its colour gathers and "B2pix+red" its per-pixel part plus the final reduction.
 
 Only blocks that run the phases are recorded (the empty-block shortcut returns before the record).
 Per kernel it also prints how the blocks landed on the chip: entries (valid slots + 1 per pixel of
@@ -26,6 +29,7 @@ import argparse  # noqa: E402
 ap = argparse.ArgumentParser()
 ap.add_argument("--config", choices=sorted(bench.CONFIGS), default="cfg2")
 ap.add_argument("--dense", action="store_true", help="the dense-fragment microbench (bench.dense_roofline's blend)")
+ap.add_argument("--split", action="store_true", help="name the split stamps (see above)")
 ap.add_argument("--save", help="also write the raw records (2 x 65536 x 12 int64) to this .npy")
 args = ap.parse_args()
 cfg = bench.CONFIGS[args.config]
@@ -56,8 +60,9 @@ def spread(name, v, unit=""):
           f"min/mean {v.min() / m:.2f}, n {len(v)})")
 
 
-for w, name, ph in ((0, "blend_fwd", ["setup", "slots", "rast", "pixel", "argmax", "out"]),
-                    (1, "blend_bwd", ["setup", "B1", "B2", "B5", "B6", "B7", "B8", "red"])):
+FWD = ["setup", "slots", "rast", "pixel", "argmax", "out"] + (["1a_load"] if args.split else [])
+BWD = ["setup", "B1", "B2", "B5", "B6", "B7", "B8", "B2pix+red" if args.split else "red"]
+for w, name, ph in ((0, "blend_fwd", FWD), (1, "blend_bwd", BWD)):
     r = rec[w][(rec[w][:, REC - 1] & 1) == 1]
     t0 = r[:, 0].min()
     st, en = (r[:, 0] - t0) / 100.0, (r[:, 1] - t0) / 100.0
@@ -74,6 +79,9 @@ for w, name, ph in ((0, "blend_fwd", ["setup", "slots", "rast", "pixel", "argmax
     for i in np.argsort(-dur)[:5]:  # the longest blocks: start, duration, phases
         print(f"  long block start {st[i]:.1f} dur {dur[i]:.1f} phases",
               dict(zip(ph, (r[i, 2:2 + len(ph)] / 2400).round(2).tolist())))
+    hv = ((r[:, REC - 1] >> 8) & 0xffffff) >= 0.8 * ((r[:, REC - 1] >> 8) & 0xffffff).max()
+    print("  heavy blocks' phase us mean", dict(zip(ph, (r[hv, 2:2 + len(ph)].mean(0) / 2400).round(2).tolist())),
+          "\n  heavy blocks' phase us max ", dict(zip(ph, (r[hv, 2:2 + len(ph)].max(0) / 2400).round(2).tolist())))
     # where the blocks ran: XCC_ID in bits 32-35 of the hw word, SE / SH / CU of HW_ID below
     ent = (r[:, REC - 1] >> 8) & 0xffffff
     disp = r[:, REC - 1] >> 32
