@@ -39,6 +39,8 @@
  *   pr_mesh_normal_consistency_fwd / _bwd, pr_chamfer_fwd / _bwd
  *       mesh_normal_consistency and chamfer_distance, the other two losses
  *       experiments/eval.py:26-31 imports from pytorch3d.loss.
+ *   pr_sample_points_fwd / _bwd
+ *       PyTorch3D 0.4.0 sample_points_from_meshes, the sampler that feeds chamfer_distance.
  */
 #ifndef PERTRENDER_H_
 #define PERTRENDER_H_
@@ -636,6 +638,58 @@ typedef struct PRChamferArgs {
 size_t pr_chamfer_workspace(int64_t N, int64_t P, int64_t Q);  /* bytes; 0 when no range split */
 int pr_chamfer_fwd(const PRChamferArgs* args, void* stream);
 int pr_chamfer_bwd(const PRChamferArgs* args, void* stream);
+
+/* Area-weighted surface sampling of a packed mesh batch (PyTorch3D 0.4.0 sample_points_from_meshes),
+ * S samples per mesh, forward and backward; no atomics, two calls with the same key give the same
+ * bits.  Additive to ABI 21.  Three uniforms u = (u0, u1, u2) determine sample s of mesh n:
+ *   face: a_f = |(v1 - v0) x (v2 - v0)| / 2 (float32); cdf = the mesh's inclusive prefix sum of a_f,
+ *     accumulated in float64 and rounded to float32 once per entry; total = cdf[last], r = u0 total;
+ *     the first f with cdf[f] > r, else the first f with cdf[f] >= total: a zero-area face is never
+ *     picked.  Areas and picks are constants of the backward.
+ *   point: su = sqrt(u1), w = (1 - su, su (1 - u2), su u2), p = w0 v0 + w1 v1 + w2 v2.
+ *   normal (optional): c / max(|c|, 2.220446049250313e-16), c = (v1 - v0) x (v2 - v1).
+ *   A mesh without faces or with total == 0 gives zero rows, face_idx -1 and no gradient.
+ * Noise: PR_NOISE_PHILOX draws one Philox4x32-R block (R = PR_PHILOX_STREAM_ROUNDS) per (n, s),
+ * counter (s, n, 0, 0x53414D50 "SAMP"), key `seed` (with `seeds`: mix64(seeds[0] ^ seed), as the
+ * blend), u_i = u01(word i); PR_NOISE_INJECTED reads `uniforms`.
+ *   pr_sample_points_fwd: a face pass (areas, in `workspace`), one workgroup per mesh scanning its
+ *     areas into `cdf` (meshes of any length, read from the device tables), one lane per (n, s).
+ *   pr_sample_points_bwd: grad_verts (overwritten) from grad_samples and optional grad_normals over
+ *     the forward's face_idx / w, whatever the noise mode was.  The caller supplies the face ->
+ *     samples CSR of this call (a stable sort of face_idx, dead rows last): one wave per face sums
+ *     its segment with fixed lane striding and a fixed tree into (F,3,3) corner gradients (in
+ *     `workspace`), the normals' gradients through the normalisation (g_c = (g_n - n (n . g_n)) / |c|
+ *     where |c| >= eps, g_n / eps otherwise), then one lane per vertex gathers over the corner CSR. */
+typedef struct PRSamplePointsArgs {
+  const float* verts;               /* (V,3) */
+  const int64_t* faces;             /* (F,3) packed */
+  const int64_t* mesh_first_face;   /* (N) first packed face of every mesh */
+  const int64_t* mesh_num_faces;    /* (N); values are clamped to the packed list */
+  int64_t N, S, V, F;
+  int32_t noise_mode;               /* PR_NOISE_PHILOX / PR_NOISE_INJECTED; fwd */
+  int32_t pad0;
+  uint64_t seed;                    /* Philox key, or the stream id under `seeds` */
+  const uint64_t* seeds;            /* device key base or NULL */
+  const float* uniforms;            /* (N,S,3) in [0,1]; PR_NOISE_INJECTED */
+  float* cdf;                       /* (F) fwd out */
+  float* samples;                   /* (N,S,3) fwd out */
+  float* normals;                   /* (N,S,3) fwd out, or NULL */
+  int32_t* face_idx;                /* (N,S) packed face or -1: fwd out (the caller sorts it for the bwd) */
+  float* w;                         /* (N,S,3) barycentric weights (0 on dead rows): fwd out, bwd in */
+  void* workspace;                  /* fwd and bwd: pr_sample_points_workspace(F) bytes */
+  size_t workspace_bytes;
+  const int64_t* face_sample_start; /* (F+1) face -> flat samples n S + s, ascending; bwd */
+  const int64_t* face_samples;      /* (N S) */
+  const int64_t* vert_corner_start; /* (V+1) vertex -> face corners t = 3 f + c, ascending; bwd */
+  const int64_t* vert_corners;      /* (3F) */
+  const float* grad_samples;        /* (N,S,3) bwd in */
+  const float* grad_normals;        /* (N,S,3) bwd in, or NULL */
+  float* grad_verts;                /* (V,3) bwd out, overwritten */
+} PRSamplePointsArgs;
+
+size_t pr_sample_points_workspace(int64_t F);  /* bytes */
+int pr_sample_points_fwd(const PRSamplePointsArgs* args, void* stream);
+int pr_sample_points_bwd(const PRSamplePointsArgs* args, void* stream);
 
 int pr_abi_version(void);
 const char* pr_last_error(void);

@@ -182,6 +182,16 @@ class PRChamferArgs(C.Structure):
                 ("grad_x", _vp), ("grad_y", _vp)]
 
 
+class PRSamplePointsArgs(C.Structure):
+    _fields_ = [("verts", _vp), ("faces", _vp), ("mesh_first_face", _vp), ("mesh_num_faces", _vp),
+                ("N", C.c_int64), ("S", C.c_int64), ("V", C.c_int64), ("F", C.c_int64),
+                ("noise_mode", C.c_int32), ("pad0", C.c_int32), ("seed", C.c_uint64), ("seeds", _vp),
+                ("uniforms", _vp), ("cdf", _vp), ("samples", _vp), ("normals", _vp), ("face_idx", _vp), ("w", _vp),
+                ("workspace", _vp), ("workspace_bytes", C.c_size_t), ("face_sample_start", _vp),
+                ("face_samples", _vp), ("vert_corner_start", _vp), ("vert_corners", _vp), ("grad_samples", _vp),
+                ("grad_normals", _vp), ("grad_verts", _vp)]
+
+
 # every symbol include/pertrender.h declares, with its argument struct (None = no args)
 EXPORTS = {
     "pr_abi_version": (C.c_int, []),
@@ -232,6 +242,9 @@ EXPORTS = {
     "pr_chamfer_workspace": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
     "pr_chamfer_fwd": (C.c_int, [C.POINTER(PRChamferArgs), _vp]),
     "pr_chamfer_bwd": (C.c_int, [C.POINTER(PRChamferArgs), _vp]),
+    "pr_sample_points_workspace": (C.c_size_t, [C.c_int64]),
+    "pr_sample_points_fwd": (C.c_int, [C.POINTER(PRSamplePointsArgs), _vp]),
+    "pr_sample_points_bwd": (C.c_int, [C.POINTER(PRSamplePointsArgs), _vp]),
 }
 ABI_VERSION = 21
 

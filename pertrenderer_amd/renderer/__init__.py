@@ -8,6 +8,7 @@ from .interp import interpolate_face_attributes
 from .io import load_obj, load_objs_as_meshes
 from .loss import chamfer_distance, mesh_edge_loss, mesh_laplacian_smoothing, mesh_normal_consistency
 from .mesh import Meshes, TexturesVertex
+from .ops import sample_points_from_meshes
 from .rasterizer import Fragments, MeshRasterizer, RasterizationSettings, rasterize_meshes
 from .renderer import BlendParams, DirectionalLights, Materials, MeshRenderer, PointLights
 from .shaders import HardPhongShader, SoftPhongShader, SoftSilhouetteShader
@@ -22,7 +23,7 @@ __all__ = [
     "TexturesVertex", "Fragments", "MeshRasterizer", "RasterizationSettings", "rasterize_meshes",
     "BlendParams", "DirectionalLights", "Materials", "MeshRenderer", "PointLights", "hard_rgb_blend",
     "sigmoid_alpha_blend", "softmax_rgb_blend", "load_objs_as_meshes", "chamfer_distance", "mesh_edge_loss",
-    "mesh_laplacian_smoothing", "mesh_normal_consistency", "HardPhongShader", "SoftPhongShader",
+    "mesh_laplacian_smoothing", "mesh_normal_consistency", "sample_points_from_meshes", "HardPhongShader", "SoftPhongShader",
     "SoftSilhouetteShader", "phong_shading", "Textures", "TexturesAtlas", "TexturesUV", "Rotate",
     "random_rotations", "so3_exp_map", "so3_exponential_map", "so3_log_map", "so3_relative_angle",
 ]

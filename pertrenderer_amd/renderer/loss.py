@@ -344,7 +344,9 @@ def _chamfer_reduce(cx, cy, x_len, y_len, weights, batch_reduction, point_reduct
 
 def _normal_terms(n, n_other, idx):
     """1 - |cos(n_i, n_other[idx_i])| (N,P); 0 where idx is -1."""
-    near = n_other.gather(1, idx.clamp(min=0).to(torch.int64)[..., None].expand(-1, -1, n_other.shape[2]))
+    # indexed, not gathered: the backward is a sorted index_put_(accumulate=True), the same bits on
+    # every call (gather's is a scatter_add on float atomics)
+    near = n_other[torch.arange(idx.shape[0], device=idx.device)[:, None], idx.clamp(min=0).to(torch.int64)]
     c = 1.0 - torch.nn.functional.cosine_similarity(n, near, dim=2, eps=1e-6).abs()
     return c.masked_fill(idx < 0, 0.0)
 

@@ -112,6 +112,14 @@ class _Topology:
             c = self._csr[kind] = (start.contiguous(), vals[order].contiguous())
         return c
 
+    def face_arange(self):
+        """arange(F + 1) int32 on the device, cached: the search keys of a per-call face -> samples
+        CSR (ops.sample_points_from_meshes' backward)."""
+        c = self._csr.get("face_arange")
+        if c is None:
+            c = self._csr["face_arange"] = torch.arange(sum(self.nfaces) + 1, dtype=torch.int32, device=self.device)
+        return c
+
     # ---- caches of the mesh regularisers (renderer/loss.py): built once per topology (building
     # may synchronise, as torch.unique does), read afterwards without a sync or an index kernel
     def _edge_keys(self):

@@ -9,6 +9,14 @@
 (b) "chamfer": chamfer_distance forward + backward at N = 1, P = Q = 5000 and 20000 (uniform clouds,
     seeded): ms per call and peak allocated memory above the inputs.
 
+(c) "sampling": sample_points_from_meshes with normals, forward + backward, and (d)
+    "deformation_step": sample -> chamfer_distance with normals + mesh_edge_loss +
+    mesh_normal_consistency + mesh_laplacian_smoothing -> backward -> SGD update, at 4 x sphere_642
+    with S = 5000 and at the 3x subdivided sphere (81 920 faces) with S = 10 000: kernels and copies
+    of one call, ms per call on the native kernels and on the torch composition
+    (NATIVE_MESHLOSS off) in the same process, and the native step replayed from a captured graph
+    with a DeviceSeed.  `--sampling` runs (c) and (d) alone.
+
     python tools/meshloss_bench.py --sweep [--out FILE]
 
 "chamfer_sweep": chamfer_distance forward alone and forward + backward at 5000 x 5000, 20000 x 20000
@@ -127,6 +135,112 @@ def chamfer(device, P, steps, repeats):
     return out
 
 
+def _sampling_shapes(device):
+    """(name, source Meshes, S): 4 x sphere_642 at S = 5000 and fine_sphere(3) (81 920 faces) at S = 10 000."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import meshgen
+    v0, f0 = meshgen.load_sphere()
+    v3, f3 = meshgen.fine_sphere(3)
+    scale = torch.tensor([1.0, 0.7, 1.3])
+    small = Meshes([(torch.tensor(v0) * scale).to(device) for _ in range(4)], [torch.tensor(f0).to(device) for _ in range(4)])
+    fine = Meshes([(torch.tensor(v3) * scale).to(device)], [torch.tensor(f3).to(device)])
+    return [("4xsphere_642", small, 5000), ("fine_sphere3", fine, 10000)]
+
+
+def _both_paths(fn):
+    """fn() under the native kernels and under the torch composition (NATIVE_MESHLOSS off)."""
+    out = {}
+    keep = L.NATIVE_MESHLOSS
+    for name, native in (("native", True), ("composition", False)):
+        L.NATIVE_MESHLOSS = native
+        try:
+            out[name] = fn()
+        finally:
+            L.NATIVE_MESHLOSS = keep
+    return out
+
+
+def sampling(device, steps, repeats):
+    """sample_points_from_meshes with normals, forward + backward to the vertices."""
+    from pertrenderer_amd.renderer import sample_points_from_meshes
+    rows = []
+    for name, src, S in _sampling_shapes(device):
+        d = torch.zeros((src.verts_packed().shape[0], 3), device=device, requires_grad=True)
+
+        def call():
+            d.grad = None
+            p, n = sample_points_from_meshes(src.offset_verts(d), S, return_normals=True)
+            (p.sum() + n[..., 0].sum()).backward()
+
+        def measure():
+            for _ in range(5):
+                call()
+            row = count_launches(call)
+            row["ms"] = spread(timed(call, steps, repeats))
+            return row
+
+        rows.append(dict(shape=name, S=S, faces=int(src.faces_packed().shape[0]), **_both_paths(measure)))
+    return rows
+
+
+def deformation_step(device, steps, repeats):
+    """sample -> Chamfer with normals + edge + normal consistency + Laplacian -> backward: ms per step
+    eager on both paths, and replayed from a captured graph with a DeviceSeed on the native path."""
+    from pertrenderer_amd import noise
+    from pertrenderer_amd.renderer import sample_points_from_meshes
+    rows = []
+    for name, src, S in _sampling_shapes(device):
+        N = len(src)
+        g = torch.Generator().manual_seed(S)
+        tgt = torch.nn.functional.normalize(torch.randn((N, S, 3), generator=g), dim=2).to(device)
+        tgt_n = tgt.clone()
+        tgt = tgt * 1.1 + 0.05
+        start = (0.02 * torch.randn(src.verts_packed().shape, generator=g)).to(device)
+
+        def step(d):
+            m = src.offset_verts(d)
+            p, n = sample_points_from_meshes(m, S, return_normals=True)
+            cd, cn = L.chamfer_distance(p, tgt, x_normals=n, y_normals=tgt_n)
+            loss = (cd + 0.1 * cn + L.mesh_edge_loss(m) + 0.01 * L.mesh_normal_consistency(m)
+                    + 0.1 * L.mesh_laplacian_smoothing(m, "uniform"))
+            d.grad = None
+            loss.backward()
+            with torch.no_grad():
+                d.add_(d.grad, alpha=-1e-4)
+
+        def measure():
+            d = start.clone().requires_grad_(True)
+            for _ in range(5):
+                step(d)
+            row = count_launches(lambda: step(d))
+            row["eager_ms"] = spread(timed(lambda: step(d), steps, repeats))
+            if not L.NATIVE_MESHLOSS:  # the captured step is the native path's claim
+                return row
+            ds = noise.DeviceSeed(device, seed=1)
+            noise.use_device_seed(ds)
+            try:
+                d = start.clone().requires_grad_(True)
+                side = torch.cuda.Stream()
+                side.wait_stream(torch.cuda.current_stream())
+                with torch.cuda.stream(side):
+                    ds.advance()
+                    step(d)
+                torch.cuda.current_stream().wait_stream(side)
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    ds.advance()
+                    step(d)
+                for _ in range(5):
+                    graph.replay()
+                row["captured_ms"] = spread(timed(graph.replay, steps, repeats))
+            finally:
+                noise.use_device_seed(None)
+            return row
+
+        rows.append(dict(shape=name, S=S, faces=int(src.faces_packed().shape[0]), **_both_paths(measure)))
+    return rows
+
+
 def chamfer_sweep(device, steps, repeats):
     from pertrenderer_amd import _native as nat
     out = dict(library=os.path.basename(nat.LIB_PATH), cases=[])
@@ -166,6 +280,7 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--out")
     ap.add_argument("--sweep", action="store_true", help="chamfer over PR_CHAMFER_SPLITS instead of (a) and (b)")
+    ap.add_argument("--sampling", action="store_true", help="(c) and (d) only")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("meshloss_bench needs a ROCm device: a CPU run gives no timing")
@@ -173,13 +288,21 @@ def main():
     if args.sweep:
         res = dict(device=torch.cuda.get_device_name(0),
                    chamfer_sweep=chamfer_sweep(device, max(args.steps // 4, 10), min(args.repeats, 5)))
+    elif args.sampling:
+        res = dict(device=torch.cuda.get_device_name(0), **_sampling_run(device, args))
     else:
         res = _default_run(device, args)
+        res.update(_sampling_run(device, args))
     line = json.dumps(res)
     print(line)
     if args.out:
         with open(args.out, "w") as fh:
             fh.write(line + "\n")
+
+
+def _sampling_run(device, args):
+    return dict(sampling=sampling(device, max(args.steps // 4, 10), args.repeats),
+                deformation_step=deformation_step(device, max(args.steps // 10, 5), args.repeats))
 
 
 def _default_run(device, args):
