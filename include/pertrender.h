@@ -41,6 +41,9 @@
  *       experiments/eval.py:26-31 imports from pytorch3d.loss.
  *   pr_sample_points_fwd / _bwd
  *       PyTorch3D 0.4.0 sample_points_from_meshes, the sampler that feeds chamfer_distance.
+ *   pr_point_mesh_fwd / _bwd
+ *       PyTorch3D 0.4.0 point_mesh_face_distance / point_mesh_edge_distance, the losses that fit
+ *       a mesh to a point cloud directly.
  */
 #ifndef PERTRENDER_H_
 #define PERTRENDER_H_
@@ -690,6 +693,74 @@ typedef struct PRSamplePointsArgs {
 size_t pr_sample_points_workspace(int64_t F);  /* bytes */
 int pr_sample_points_fwd(const PRSamplePointsArgs* args, void* stream);
 int pr_sample_points_bwd(const PRSamplePointsArgs* args, void* stream);
+
+/* Point-to-mesh distances (the cores of PyTorch3D 0.4.0 point_mesh_face_distance, prim 0, and
+ * point_mesh_edge_distance, prim 1) between N point clouds and N meshes, both packed, both
+ * directions per call; no atomics, two calls give the same bits.  Additive to ABI 21.
+ * Primitive m is the triangle verts[prims[m,0..2]] or the segment verts[prims[m,0..1]]; batch
+ * element n owns points [cloud_first[n], + cloud_count[n]) and primitives [mesh_first[n],
+ * + mesh_count[n]) (device tables, read by the kernels and clamped to the packed lists;
+ * max_points / max_prims are the host's upper bounds of the counts and size the grid).
+ * cloud_first NULL: a padded batch, cloud n at n max_points (P = N max_points); cloud_count NULL:
+ * every cloud has max_points points.
+ *   Closest point: the Voronoi region of p from the signs of the edge dot products (Ericson's
+ *   closest-point-on-triangle tests, in his order) gives weights w on the corners; in a vertex or
+ *   edge region r = sum w_i (p - v_i); in the interior n = (v1 - v0) x (v2 - v0),
+ *   t = n . (p - v0) / |n|^2, r = t n and w from the projected point's cross products against n;
+ *   d^2 = |r|^2.  A triangle with |n|^2 <= 1e-30 is evaluated as its segments (v0 v1), (v1 v2),
+ *   (v2 v0), the first of equal ones; a zero-length segment as its first endpoint.
+ *   pr_point_mesh_fwd: dist_p[i] = min over the primitives m of point i's mesh of d^2(i, m), idx_p[i]
+ *     the lowest packed m that attains it, w_p[i] its weights (a segment uses the first two);
+ *     dist_m / idx_m / w_m the same for every primitive over the points of its cloud.  A query
+ *     with nothing on the other side, and a padding row of a padded batch, gets 0, -1 and zero
+ *     weights.  A NaN candidate is never chosen; a live query for which no d^2 compares below +inf
+ *     gets a non-finite distance (NaN if the query itself is NaN, else +inf), idx -1 and gradient 0,
+ *     as in pr_chamfer_fwd.  With few queries the other side is cut into ranges over a further grid
+ *     dimension (count from the shape; PR_POINTMESH_SPLITS overrides it, read per call) and the
+ *     partial results are merged through `workspace` in range order with the same tie rule.
+ *   pr_point_mesh_bwd: d d^2 / d p = 2 r, d d^2 / d v_i = -2 w_i r with the forward's weights.
+ *     grad_points[i] (overwritten) = 2 grad_dist_p[i] r(i, idx_p[i]) + sum over the primitives m that
+ *     chose i, ascending, of 2 grad_dist_m[m] r(i, m); per-primitive corner gradients (in
+ *     `workspace`): one wave per primitive sums -2 grad_dist_p[i] w_p[i] r(i, m) over the points
+ *     that chose it with fixed lane striding and a fixed tree, plus its own term; grad_verts
+ *     (overwritten) gathers them per vertex.  The caller supplies the two CSRs of this call
+ *     (stable sorts of idx_p and idx_m, rows with -1 last) and the vertex -> corners CSR. */
+typedef struct PRPointMeshArgs {
+  const float* points;               /* (P,3) packed */
+  const int64_t* cloud_first;        /* (N) or NULL (padded batch) */
+  const int64_t* cloud_count;        /* (N) or NULL (max_points each) */
+  const float* verts;                /* (V,3) */
+  const int64_t* prims;              /* (M,3) faces or (M,2) edges: packed vertex ids */
+  const int64_t* mesh_first;         /* (N) first packed primitive of every mesh; fwd */
+  const int64_t* mesh_count;         /* (N); fwd */
+  int64_t N, P, V, M;
+  int64_t max_points, max_prims;     /* upper bounds of the per-element counts, <= P / M */
+  int32_t prim;                      /* 0 faces, 1 edges */
+  int32_t pad0;
+  float* dist_p;                     /* (P) fwd out */
+  int32_t* idx_p;                    /* (P) packed primitive or -1: fwd out, bwd in */
+  float* w_p;                        /* (P,3) fwd out, bwd in */
+  float* dist_m;                     /* (M) fwd out */
+  int32_t* idx_m;                    /* (M) packed point or -1: fwd out, bwd in */
+  float* w_m;                        /* (M,3) fwd out, bwd in */
+  void* workspace;                   /* fwd and bwd: pr_point_mesh_workspace bytes */
+  size_t workspace_bytes;
+  const int64_t* prim_point_start;   /* (M+1) primitive -> the points that chose it, ascending; bwd */
+  const int64_t* prim_points;        /* (P) */
+  const int64_t* point_prim_start;   /* (P+1) point -> the primitives that chose it, ascending; bwd */
+  const int64_t* point_prims;        /* (M) */
+  const int64_t* vert_corner_start;  /* (V+1) vertex -> corners t = K m + c (K = 3 or 2), ascending; bwd */
+  const int64_t* vert_corners;       /* (K M) */
+  const float* grad_dist_p;          /* (P) bwd in */
+  const float* grad_dist_m;          /* (M) bwd in */
+  float* grad_points;                /* (P,3) bwd out, overwritten */
+  float* grad_verts;                 /* (V,3) bwd out, overwritten */
+} PRPointMeshArgs;
+
+size_t pr_point_mesh_workspace(int32_t prim, int64_t N, int64_t P, int64_t M, int64_t max_points,
+                               int64_t max_prims);  /* bytes; 0 for sizes the entry points reject */
+int pr_point_mesh_fwd(const PRPointMeshArgs* args, void* stream);
+int pr_point_mesh_bwd(const PRPointMeshArgs* args, void* stream);
 
 int pr_abi_version(void);
 const char* pr_last_error(void);

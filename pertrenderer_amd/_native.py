@@ -192,6 +192,17 @@ class PRSamplePointsArgs(C.Structure):
                 ("grad_normals", _vp), ("grad_verts", _vp)]
 
 
+class PRPointMeshArgs(C.Structure):
+    _fields_ = [("points", _vp), ("cloud_first", _vp), ("cloud_count", _vp), ("verts", _vp), ("prims", _vp),
+                ("mesh_first", _vp), ("mesh_count", _vp), ("N", C.c_int64), ("P", C.c_int64), ("V", C.c_int64),
+                ("M", C.c_int64), ("max_points", C.c_int64), ("max_prims", C.c_int64), ("prim", C.c_int32),
+                ("pad0", C.c_int32), ("dist_p", _vp), ("idx_p", _vp), ("w_p", _vp), ("dist_m", _vp), ("idx_m", _vp),
+                ("w_m", _vp), ("workspace", _vp), ("workspace_bytes", C.c_size_t), ("prim_point_start", _vp),
+                ("prim_points", _vp), ("point_prim_start", _vp), ("point_prims", _vp), ("vert_corner_start", _vp),
+                ("vert_corners", _vp), ("grad_dist_p", _vp), ("grad_dist_m", _vp), ("grad_points", _vp),
+                ("grad_verts", _vp)]
+
+
 # every symbol include/pertrender.h declares, with its argument struct (None = no args)
 EXPORTS = {
     "pr_abi_version": (C.c_int, []),
@@ -245,6 +256,9 @@ EXPORTS = {
     "pr_sample_points_workspace": (C.c_size_t, [C.c_int64]),
     "pr_sample_points_fwd": (C.c_int, [C.POINTER(PRSamplePointsArgs), _vp]),
     "pr_sample_points_bwd": (C.c_int, [C.POINTER(PRSamplePointsArgs), _vp]),
+    "pr_point_mesh_workspace": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
+    "pr_point_mesh_fwd": (C.c_int, [C.POINTER(PRPointMeshArgs), _vp]),
+    "pr_point_mesh_bwd": (C.c_int, [C.POINTER(PRPointMeshArgs), _vp]),
 }
 ABI_VERSION = 21
 

@@ -6,9 +6,11 @@ from .cameras import (FoVPerspectiveCameras, OpenGLPerspectiveCameras, camera_po
 from .blending import hard_rgb_blend, sigmoid_alpha_blend, softmax_rgb_blend
 from .interp import interpolate_face_attributes
 from .io import load_obj, load_objs_as_meshes
-from .loss import chamfer_distance, mesh_edge_loss, mesh_laplacian_smoothing, mesh_normal_consistency
+from .loss import (chamfer_distance, mesh_edge_loss, mesh_laplacian_smoothing, mesh_normal_consistency,
+                   point_mesh_edge_distance, point_mesh_face_distance)
 from .mesh import Meshes, TexturesVertex
 from .ops import sample_points_from_meshes
+from .pointclouds import Pointclouds
 from .rasterizer import Fragments, MeshRasterizer, RasterizationSettings, rasterize_meshes
 from .renderer import BlendParams, DirectionalLights, Materials, MeshRenderer, PointLights
 from .shaders import HardPhongShader, SoftPhongShader, SoftSilhouetteShader
@@ -23,7 +25,8 @@ __all__ = [
     "TexturesVertex", "Fragments", "MeshRasterizer", "RasterizationSettings", "rasterize_meshes",
     "BlendParams", "DirectionalLights", "Materials", "MeshRenderer", "PointLights", "hard_rgb_blend",
     "sigmoid_alpha_blend", "softmax_rgb_blend", "load_objs_as_meshes", "chamfer_distance", "mesh_edge_loss",
-    "mesh_laplacian_smoothing", "mesh_normal_consistency", "sample_points_from_meshes", "HardPhongShader", "SoftPhongShader",
+    "mesh_laplacian_smoothing", "mesh_normal_consistency", "point_mesh_edge_distance", "point_mesh_face_distance",
+    "Pointclouds", "sample_points_from_meshes", "HardPhongShader", "SoftPhongShader",
     "SoftSilhouetteShader", "phong_shading", "Textures", "TexturesAtlas", "TexturesUV", "Rotate",
     "random_rotations", "so3_exp_map", "so3_exponential_map", "so3_log_map", "so3_relative_angle",
 ]

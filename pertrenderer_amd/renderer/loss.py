@@ -8,7 +8,9 @@ with float32 inputs all four losses run on the native kernels (the Laplacian, th
 normal consistency in csrc/pr_meshloss.hip: per-vertex / per-face CSR gathers; chamfer_distance's
 nearest neighbours in csrc/pr_chamfer.hip; no atomics, bitwise reproducible);
 PR_NATIVE_MESHLOSS=0 (or NATIVE_MESHLOSS = False), CPU tensors and other dtypes take the torch
-composition of the same formulas.  Parity with PyTorch3D is unpinned (not installable here)."""
+composition of the same formulas.  point_mesh_face_distance and point_mesh_edge_distance (the
+losses between a mesh and a Pointclouds, csrc/pr_pointmesh.hip) follow the same rules.  Parity
+with PyTorch3D is unpinned (not installable here)."""
 import os
 
 import torch
@@ -402,3 +404,321 @@ def chamfer_distance(x, y, batch_reduction="mean", point_reduction="mean", *, x_
     if x_normals is None:
         return loss, None
     return loss, _chamfer_reduce(_normal_terms(x_normals, y_normals, ix), _normal_terms(y_normals, x_normals, iy), *args)
+
+
+# ------------------------------------------------------------------ point-to-mesh distances
+# The closest point of a primitive (csrc/pr_pointmesh.hip states the same arithmetic): the Voronoi
+# region of p from the signs of the edge dot products (Ericson's closest-point-on-triangle tests, in
+# his order) gives the weights w of the closest point; in a vertex or edge region
+# r = sum w_i (p - v_i); in the interior the point is projected first, n = (v1 - v0) x (v2 - v0),
+# t = n . (p - v0) / |n|^2, r = t n, and w comes from the projected point's cross products against n;
+# d^2 = |r|^2.  A triangle with |n|^2 <= _DEGENERATE is evaluated as its three segments, a
+# zero-length segment as its first endpoint.  Choosing the region by comparing squared distances
+# would lose half of float32's digits.
+_DEGENERATE = 1e-30
+_PAIRS_PER_CHUNK = 1 << 19  # (point, primitive) pairs per block of the composition: ~400 B of float32 temporaries each, ~200 MB
+_PRIMS = {"faces": 0, "edges": 1}
+
+
+def _dot(a, b):
+    return a[..., 0] * b[..., 0] + a[..., 1] * b[..., 1] + a[..., 2] * b[..., 2]
+
+
+def _ratio(num, den):
+    return torch.where(den > 0, num / torch.where(den > 0, den, torch.ones_like(den)), torch.zeros_like(num))
+
+
+def _closest_on_segment(p, a, b):
+    """(d^2, w (...,3) = (1 - v, v, 0), r) of the points p against the segments (a, b), broadcast."""
+    ab, ap, bp = b - a, p - a, p - b
+    d1, d3 = _dot(ab, ap), _dot(ab, bp)
+    v = torch.where(d1 <= 0, torch.zeros_like(d1), torch.where(d3 >= 0, torch.ones_like(d1), d1 / (d1 - d3)))
+    w = torch.stack([1 - v, v, torch.zeros_like(v)], -1)
+    r = ap * w[..., 0:1] + bp * w[..., 1:2]
+    return _dot(r, r), w, r
+
+
+def _closest_on_triangle(p, a, b, c):
+    """(d^2, w (...,3), r) of the points p against the triangles (a, b, c), broadcast."""
+    ab, ac, ap, bp, cp = b - a, c - a, p - a, p - b, p - c
+    d1, d2, d3, d4, d5, d6 = _dot(ab, ap), _dot(ac, ap), _dot(ab, bp), _dot(ac, bp), _dot(ab, cp), _dot(ac, cp)
+    n = torch.cross(ab.expand_as(ap), ac.expand_as(ap), dim=-1)
+    n2 = _dot(n, n)
+    flat = ~(n2 > _DEGENERATE)
+    inv = torch.where(flat, torch.zeros_like(n2), 1.0 / torch.where(flat, torch.ones_like(n2), n2))
+    t = _dot(n, ap) * inv
+    r_in = n * t[..., None]
+    q = ap - r_in
+    w1, w2 = _dot(n, torch.cross(q, ac.expand_as(q), dim=-1)) * inv, _dot(n, torch.cross(ab.expand_as(q), q, dim=-1)) * inv
+    one, zero = torch.ones_like(d1), torch.zeros_like(d1)
+    st = lambda x, y, z: torch.stack([x, y, z], -1)  # noqa: E731
+    vab, vac, vbc = _ratio(d1, d1 - d3), _ratio(d2, d2 - d6), _ratio(d4 - d3, (d4 - d3) + (d5 - d6))
+    regions = [((d1 <= 0) & (d2 <= 0), st(one, zero, zero)),
+               ((d3 >= 0) & (d4 <= d3), st(zero, one, zero)),
+               ((d1 * d4 - d3 * d2 <= 0) & (d1 >= 0) & (d3 <= 0), st(1 - vab, vab, zero)),
+               ((d6 >= 0) & (d5 <= d6), st(zero, zero, one)),
+               ((d5 * d2 - d1 * d6 <= 0) & (d2 >= 0) & (d6 <= 0), st(1 - vac, zero, vac)),
+               ((d3 * d6 - d5 * d4 <= 0) & (d4 - d3 >= 0) & (d5 - d6 >= 0), st(zero, 1 - vbc, vbc))]
+    w, inside = st(1 - w1 - w2, w1, w2), torch.ones_like(d1, dtype=torch.bool)
+    for cond, wr in reversed(regions):  # applied last to first: the earliest test of Ericson's order wins
+        w = torch.where(cond[..., None], wr, w)
+        inside = inside & ~cond
+    r = torch.where(inside[..., None], r_in, ap * w[..., 0:1] + bp * w[..., 1:2] + cp * w[..., 2:3])
+    d = _dot(r, r)
+    if bool(flat.any()):  # the first of the three segments that is nearest
+        ds, ws, rs = _closest_on_segment(p, a, b)
+        for (x, y), perm in (((b, c), (2, 0, 1)), ((c, a), (1, 2, 0))):
+            d2_, w2_, r2_ = _closest_on_segment(p, x, y)
+            less = d2_ < ds
+            ds, rs = torch.where(less, d2_, ds), torch.where(less[..., None], r2_, rs)
+            ws = torch.where(less[..., None], w2_[..., list(perm)], ws)
+        d, w, r = torch.where(flat, ds, d), torch.where(flat[..., None], ws, w), torch.where(flat[..., None], rs, r)
+    return d, w, r
+
+
+def _closest(p, pv):
+    """p (...,3) against the primitives pv (...,K,3): triangles (K = 3) or segments (K = 2)."""
+    if pv.shape[-2] == 3:
+        return _closest_on_triangle(p, pv[..., 0, :], pv[..., 1, :], pv[..., 2, :])
+    return _closest_on_segment(p, pv[..., 0, :], pv[..., 1, :])
+
+
+def _is_nan_row(t):
+    return (t != t).reshape(t.shape[0], -1).any(dim=1)
+
+
+def _missed(dist, found, query_nan, searched):
+    """A query that chose nothing: 0 when it had nothing to search, else NaN if it is NaN itself, +inf otherwise."""
+    miss = torch.where(query_nan, torch.full_like(dist, float("nan")), torch.full_like(dist, float("inf")))
+    return torch.where(found, dist, miss if searched else torch.zeros_like(dist))
+
+
+def _point_mesh_nn_torch(points, verts, prims, cloud_ranges, mesh_ranges):
+    """The torch composition of _PointMeshFn on packed inputs, in the points' dtype: (dist_p (P),
+    dist_m (M), idx_p, idx_m int64, w_p (P,3), w_m (M,3)).  The ranges are Python (first, count)
+    pairs per batch element.  The search runs without autograd in blocks of at most
+    _PAIRS_PER_CHUNK pairs; the chosen pairs are evaluated once more, and the gradient is attached
+    in envelope form: d d^2 / d p = 2 r, d d^2 / d v_i = -2 w_i r, r and w constants."""
+    P, M = points.shape[0], prims.shape[0]
+    dev, inf = points.device, float("inf")
+    dist_p, dist_m = points.new_zeros(P), points.new_zeros(M)
+    idx_p = torch.full((P,), -1, dtype=torch.int64, device=dev)
+    idx_m = torch.full((M,), -1, dtype=torch.int64, device=dev)
+    with torch.no_grad():
+        pd, pv_all = points.detach(), verts.detach()[prims]
+        for (pf, pc), (mf, mc) in zip(cloud_ranges, mesh_ranges):
+            if pc == 0 or mc == 0:
+                continue
+            pv = pv_all[mf:mf + mc]
+            best_m = torch.full((mc,), inf, dtype=points.dtype, device=dev)
+            arg_m = torch.full((mc,), -1, dtype=torch.int64, device=dev)
+            step = max(1, _PAIRS_PER_CHUNK // mc)
+            for c0 in range(pf, pf + pc, step):
+                c1 = min(c0 + step, pf + pc)
+                d = _closest(pd[c0:c1, None], pv[None])[0]
+                d = torch.where(d != d, torch.full_like(d, inf), d)  # a NaN candidate is never chosen
+                mp, mm = d.min(dim=1), d.min(dim=0)  # the first minimum: the lowest index
+                dist_p[c0:c1] = mp.values
+                idx_p[c0:c1] = torch.where(mp.values < inf, mp.indices + mf, torch.full_like(mp.indices, -1))
+                less = mm.values < best_m  # strict, blocks in ascending order: the lowest index
+                best_m, arg_m = torch.where(less, mm.values, best_m), torch.where(less, mm.indices + c0, arg_m)
+            dist_m[mf:mf + mc], idx_m[mf:mf + mc] = best_m, arg_m
+            dist_p[pf:pf + pc] = _missed(dist_p[pf:pf + pc], idx_p[pf:pf + pc] >= 0, _is_nan_row(pd[pf:pf + pc]), True)
+            dist_m[mf:mf + mc] = _missed(best_m, arg_m >= 0, _is_nan_row(pv), True)
+        _, w_p, r_p = _closest(pd, pv_all[idx_p.clamp(min=0)])
+        _, w_m, r_m = _closest(pd[idx_m.clamp(min=0)], pv_all)
+        live_p, live_m = idx_p >= 0, idx_m >= 0
+        zero = torch.zeros((), dtype=points.dtype, device=dev)
+        w_p, r_p = torch.where(live_p[:, None], w_p, zero), torch.where(live_p[:, None], r_p, zero)
+        w_m, r_m = torch.where(live_m[:, None], w_m, zero), torch.where(live_m[:, None], r_m, zero)
+    K = prims.shape[1]
+    pv_all = verts[prims]
+
+    def attach(dist, live, p, pv, w, r):
+        # value dist, gradient 2 r . d (p - sum w_i v_i): the difference below is exactly 0 (a query
+        # that chose nothing is left out: its coordinates may be NaN)
+        delta = p - (pv * w[:, :K, None]).sum(dim=1)
+        return dist + torch.where(live, 2.0 * (r * (delta - delta.detach())).sum(dim=-1), zero)
+
+    dist_p = attach(dist_p, live_p, points, pv_all[idx_p.clamp(min=0)], w_p, r_p)
+    dist_m = attach(dist_m, live_m, points[idx_m.clamp(min=0)], pv_all, w_m, r_m)
+    return dist_p, dist_m, idx_p, idx_m, w_p, w_m
+
+
+class _PointMeshFn(torch.autograd.Function):
+    """(points (P,3) packed, verts (V,3)) -> (dist_p (P), dist_m (M), idx_p (P), idx_m (M) int32 packed
+    or -1, w_p (P,3), w_m (M,3)) for the topology's faces or edges (pr_point_mesh_fwd/bwd).  The
+    clouds are given by device tables (cloud_first, cloud_count) and the host bound max_points;
+    cloud_first None is a padded batch of max_points rows per cloud.  The backward sorts idx_p and
+    idx_m on the device into the two CSRs of the call: once-differentiable, no host read."""
+
+    @staticmethod
+    def _args(nat, p, v, tab, kind, cloud_first, cloud_count, max_points, idx_p, idx_m, w_p, w_m):
+        a = nat.PRPointMeshArgs()
+        a.points, a.cloud_first, a.cloud_count = nat.ptr(p), nat.ptr(cloud_first), nat.ptr(cloud_count)
+        a.verts, a.prims, a.mesh_first, a.mesh_count = nat.ptr(v), nat.ptr(tab["prims"]), nat.ptr(tab["first"]), nat.ptr(tab["count"])
+        a.N, a.P, a.V, a.M = len(tab["counts"]), p.shape[0], v.shape[0], tab["prims"].shape[0]
+        a.max_points, a.max_prims, a.prim = max_points, max(tab["counts"]), _PRIMS[kind]
+        a.idx_p, a.idx_m, a.w_p, a.w_m = nat.ptr(idx_p), nat.ptr(idx_m), nat.ptr(w_p), nat.ptr(w_m)
+        nbytes = nat.load().pr_point_mesh_workspace(a.prim, a.N, a.P, a.M, a.max_points, a.max_prims)
+        ws = nat.workspace(nbytes, p.device)
+        a.workspace, a.workspace_bytes = nat.ptr(ws), nbytes
+        return a, ws  # ws: kept alive by the caller's frame until the launch is enqueued
+
+    @staticmethod
+    def forward(ctx, points, verts, topo, kind, cloud_first, cloud_count, max_points):
+        from .. import _native as nat
+        nat.require_device(points, verts, cloud_first, cloud_count)
+        p, v = nat.dense(points, torch.float32), nat.dense(verts, torch.float32)
+        cf = None if cloud_first is None else nat.dense(cloud_first, torch.int64)
+        cc = None if cloud_count is None else nat.dense(cloud_count, torch.int64)
+        tab = topo.prim_tables(kind)
+        P, M = p.shape[0], tab["prims"].shape[0]
+        new = lambda shape, dtype=torch.float32: torch.empty(shape, dtype=dtype, device=p.device)  # noqa: E731
+        dist_p, dist_m, w_p, w_m = new((P,)), new((M,)), new((P, 3)), new((M, 3))
+        idx_p, idx_m = new((P,), torch.int32), new((M,), torch.int32)
+        a, ws = _PointMeshFn._args(nat, p, v, tab, kind, cf, cc, max_points, idx_p, idx_m, w_p, w_m)  # noqa: F841
+        a.dist_p, a.dist_m = nat.ptr(dist_p), nat.ptr(dist_m)
+        nat.call("pr_point_mesh_fwd", "pr_point_mesh_fwd", p, a)
+        ctx.save_for_backward(p, v, idx_p, idx_m, w_p, w_m)
+        ctx.topo, ctx.kind, ctx.clouds = topo, kind, (cf, cc, max_points)
+        ctx.mark_non_differentiable(idx_p, idx_m, w_p, w_m)
+        return dist_p, dist_m, idx_p, idx_m, w_p, w_m
+
+    @staticmethod
+    def _csr(idx, rows, arange):
+        """rows -> the entries of idx that name them, ascending (a stable device sort; -1 last)."""
+        key = torch.where(idx < 0, rows, idx)
+        order = torch.argsort(key, stable=True)
+        return torch.searchsorted(key[order].contiguous(), arange), order
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_p, g_m, *_unused):
+        from .. import _native as nat
+        p, v, idx_p, idx_m, w_p, w_m = ctx.saved_tensors
+        topo, kind = ctx.topo, ctx.kind
+        tab = topo.prim_tables(kind)
+        P, M = p.shape[0], tab["prims"].shape[0]
+        g_p = torch.zeros_like(w_p[:, 0]) if g_p is None else nat.dense(g_p, torch.float32)
+        g_m = torch.zeros_like(w_m[:, 0]) if g_m is None else nat.dense(g_m, torch.float32)
+        gp, gv = torch.empty_like(p), torch.empty_like(v)
+        a, ws = _PointMeshFn._args(nat, p, v, tab, kind, *ctx.clouds, idx_p, idx_m, w_p, w_m)  # noqa: F841
+        prim_start, prim_points = _PointMeshFn._csr(idx_p, M, tab["arange"])
+        point_start, point_prims = _PointMeshFn._csr(idx_m, P, torch.arange(P + 1, dtype=torch.int32, device=p.device))
+        a.prim_point_start, a.prim_points = nat.ptr(prim_start), nat.ptr(prim_points)
+        a.point_prim_start, a.point_prims = nat.ptr(point_start), nat.ptr(point_prims)
+        csr = topo.corner_csr("gather") if kind == "faces" else topo.edge_end_csr()
+        a.vert_corner_start, a.vert_corners = nat.ptr(csr[0]), nat.ptr(csr[1])
+        a.grad_dist_p, a.grad_dist_m, a.grad_points, a.grad_verts = nat.ptr(g_p), nat.ptr(g_m), nat.ptr(gp), nat.ptr(gv)
+        nat.call("pr_point_mesh_bwd", "pr_point_mesh_bwd", p, a)
+        return gp, gv, None, None, None, None, None
+
+
+def _point_mesh_inputs(meshes, pcls, lengths):
+    """Checked inputs of the point-to-mesh losses: (points (P,3) packed, cloud_first, cloud_count
+    (device tensors or None), max_points, host (first, count) pairs or None, dtype -> the per-point
+    weights 1 / (N P_n) as a (P,) tensor or a float)."""
+    from .mesh import Meshes
+    from .pointclouds import Pointclouds
+    if not isinstance(meshes, Meshes):
+        raise ValueError(f"meshes must be a Meshes, got {type(meshes).__name__}")
+    N = len(meshes)
+    if N == 0:
+        raise ValueError("meshes is empty")
+    v = meshes.verts_packed()
+    if not v.is_floating_point() or v.dim() != 2 or v.shape[1] != 3:
+        raise ValueError(f"vertices must be floating point (V,3), got {v.dtype} {tuple(v.shape)}")
+    if isinstance(pcls, Pointclouds):
+        if lengths is not None:
+            raise ValueError("lengths goes with a padded (N,P,3) tensor, not with a Pointclouds")
+        if len(pcls) != N:
+            raise ValueError(f"meshes and pcls must have the same batch size, got {N} and {len(pcls)}")
+        points = pcls.points_packed()
+        if points.device != v.device:
+            raise ValueError(f"pcls is on {points.device}, the meshes on {v.device}")
+        ranges, off = [], 0
+        for n in pcls.npoints:
+            ranges.append((off, n))
+            off += n
+        return (points, pcls.cloud_to_packed_first_idx(), pcls.num_points_per_cloud(), max(pcls.npoints), ranges,
+                pcls.loss_weights)
+    if not torch.is_tensor(pcls) or pcls.dim() != 3 or pcls.shape[2] != 3:
+        raise ValueError("pcls must be a Pointclouds or a padded (N,P,3) tensor, got "
+                         f"{tuple(pcls.shape) if torch.is_tensor(pcls) else type(pcls).__name__}")
+    if pcls.shape[0] != N:
+        raise ValueError(f"meshes and pcls must have the same batch size, got {N} and {pcls.shape[0]}")
+    if pcls.device != v.device:
+        raise ValueError(f"pcls is on {pcls.device}, the meshes on {v.device}")
+    P = pcls.shape[1]
+    if lengths is None:
+        return pcls.reshape(-1, 3), None, None, P, [(n * P, P) for n in range(N)], lambda dtype: 1.0 / (N * max(P, 1))
+    if not torch.is_tensor(lengths) or tuple(lengths.shape) != (N,) or lengths.is_floating_point() or lengths.dtype == torch.bool:
+        raise ValueError(f"lengths must be an integer tensor of shape ({N},)")
+    if lengths.device != v.device:
+        raise ValueError(f"lengths is on {lengths.device}, the meshes on {v.device}")
+    count = lengths.to(torch.int64).clamp(0, P)  # read on the device, as chamfer_distance's lengths
+    return (pcls.reshape(-1, 3), None, count, P, None,
+            lambda dtype: (1.0 / (N * count.clamp(min=1).to(torch.float64))).to(dtype)[:, None].expand(N, P).reshape(-1))
+
+
+def _point_mesh_nn(meshes, pcls, kind, lengths=None):
+    """(dist_p (P), dist_m (M), idx_p, idx_m, w_p (P,3), w_m (M,3), the points' and the primitives'
+    loss weights 1 / (N P_n), 1 / (N M_n)) on packed points and primitives ("faces" / "edges"); a padded tensor is packed row by row, its
+    padding rows get 0 and -1.  Native on a ROCm device with float32 inputs, else the composition."""
+    points, cloud_first, cloud_count, max_points, ranges, wp = _point_mesh_inputs(meshes, pcls, lengths)
+    v, topo = meshes.verts_packed(), meshes._topo
+    tab = topo.prim_tables(kind)
+    P, M, N = points.shape[0], tab["prims"].shape[0], len(meshes)
+    if P == 0 or M == 0:  # nothing on one side: every term is 0
+        z = points.sum() * 0.0 + v.sum() * 0.0
+        return (z + points.new_zeros(P), z + points.new_zeros(M), torch.full((P,), -1, dtype=torch.int64, device=v.device),
+                torch.full((M,), -1, dtype=torch.int64, device=v.device), points.new_zeros((P, 3)), points.new_zeros((M, 3)),
+                wp(points.dtype), topo.prim_loss_weights(kind, points.dtype))
+    if (_native(v) and points.dtype == torch.float32 and N <= 32767 and P <= 2 ** 31 - 1 and 16 * M <= 2 ** 31 - 1):
+        out = _PointMeshFn.apply(points, v, topo, kind, cloud_first, cloud_count, max_points)
+    else:
+        if ranges is None:  # the composition slices on the host: one read of the lengths
+            ranges = [(n * max_points, int(c)) for n, c in enumerate(cloud_count.tolist())]
+        mesh_ranges, off = [], 0
+        for c in tab["counts"]:
+            mesh_ranges.append((off, c))
+            off += c
+        out = _point_mesh_nn_torch(points, v.to(points.dtype), tab["prims"], ranges, mesh_ranges)
+    return (*out, wp(out[0].dtype), topo.prim_loss_weights(kind, out[0].dtype))
+
+
+def _point_mesh_distance(meshes, pcls, kind, lengths):
+    dist_p, dist_m, _, _, _, _, wp, wm = _point_mesh_nn(meshes, pcls, kind, lengths)
+    return (dist_p * wp).sum() + (dist_m * wm).sum()
+
+
+def point_mesh_face_distance(meshes, pcls, *, lengths=None):
+    """Squared point-to-face distance between meshes and point clouds, both ways (PyTorch3D 0.4.0
+    point_mesh_face_distance's reductions): a 0-d loss
+        (1/N) sum_n [ (1/P_n) sum_{p in cloud n} d^2(p, mesh n) + (1/F_n) sum_{f in mesh n} d^2(f, cloud n) ],
+    d^2(p, mesh) the minimum over the mesh's triangles of the squared distance to the triangle,
+    d^2(f, cloud) the minimum over the cloud's points; the lowest index wins on equal values.
+
+    `pcls` is a Pointclouds, or a padded (N,P,3) tensor with `lengths` (N,) int64 (read on the
+    device; None: full).  A cloud or mesh with nothing on the other side contributes 0.  The
+    closest point comes from the Voronoi region of the point (the signs of the edge dot products,
+    Ericson's order); in the interior the point is projected on the plane first; a triangle with
+    |n|^2 <= 1e-30 is evaluated as its three segments.  Gradients are the envelope form
+    d d^2 / d p = 2 r, d d^2 / d v_i = -2 w_i r with the closest point's weights as constants.
+
+    On a ROCm device with float32 inputs the search and its backward run on the native kernels
+    (csrc/pr_pointmesh.hip: no (P,F) matrix, no atomics, bitwise reproducible, capturable after one
+    call on the topology); otherwise (CPU, other dtypes, PR_NATIVE_MESHLOSS=0) a torch composition
+    of the same formulas, in blocks over the points.  On non-finite input both paths follow
+    chamfer_distance's kernels: a NaN candidate is never chosen, and a query that can choose
+    nothing gets a non-finite distance and no gradient.  Arguments are checked (ValueError) before
+    anything is launched.  Parity with PyTorch3D is unpinned (not installable here)."""
+    return _point_mesh_distance(meshes, pcls, "faces", lengths)
+
+
+def point_mesh_edge_distance(meshes, pcls, *, lengths=None):
+    """point_mesh_face_distance with the meshes' unique edges (edges_packed(): segments) in place of
+    their faces: (1/N) sum_n [ (1/P_n) sum_p d^2(p, edges of mesh n) + (1/E_n) sum_e d^2(e, cloud n) ].
+    A zero-length edge is evaluated as its first endpoint."""
+    return _point_mesh_distance(meshes, pcls, "edges", lengths)

@@ -194,6 +194,48 @@ class _Topology:
             self._pair_csr = (start.contiguous(), dst[order].contiguous())
         return self._pair_csr
 
+    # ---- caches of the point-to-mesh losses (loss.point_mesh_face_distance / _edge_distance)
+    def edge_end_csr(self):
+        """Vertex -> edge-end index (CSR) of edges_packed(): (start (V+1), ends (2E)) int64, the ends
+        t = 2 e + c of vertex v at ends[start[v]:start[v+1]] in increasing t.  The counterpart of
+        corner_csr("gather") for per-edge gradients; built once on the device (stable sort)."""
+        c = self._csr.get("edge_ends")
+        if c is None:
+            keys = self.edges_packed().reshape(-1)
+            order = torch.argsort(keys, stable=True)
+            start = torch.searchsorted(keys[order].contiguous(), torch.arange(sum(self.nverts) + 1, device=keys.device))
+            c = self._csr["edge_ends"] = (start.contiguous(), order.contiguous())
+        return c
+
+    def prim_tables(self, kind):
+        """The packed primitives of `kind` ("faces" / "edges") and their per-mesh tables, cached:
+        dict(prims (M,K) int64, first (N) and count (N) int64 device tensors, counts (the same as
+        Python ints), arange (M+1) int32).  Edges are in
+        lexicographic order, so a mesh's edges are contiguous like its faces."""
+        t = self._csr.get(("prims", kind))
+        if t is None:
+            if kind == "faces":
+                prims, idx, counts = self.faces_packed(), self.index_tensors(), list(self.nfaces)
+                first, count = idx["first"], idx["nfaces"]
+            else:
+                prims, count = self.edges_packed(), self.num_edges_per_mesh()
+                first, counts = torch.cumsum(count, 0) - count, [int(c) for c in count.tolist()]
+            t = self._csr[("prims", kind)] = dict(
+                prims=prims, first=first.contiguous(), count=count.contiguous(), counts=counts,
+                arange=torch.arange(sum(counts) + 1, dtype=torch.int32, device=self.device))
+        return t
+
+    def prim_loss_weights(self, kind, dtype=F32):
+        """(M,) 1 / (N M_n) in `dtype`, n the packed primitive's mesh, cached: the per-primitive
+        weight of the point-to-mesh losses."""
+        w = self._weights.get((kind, dtype))
+        if w is None:
+            counts = self.prim_tables(kind)["counts"]
+            per = torch.tensor([1.0 / (len(counts) * max(c, 1)) for c in counts], dtype=torch.float64)
+            w = torch.repeat_interleave(per, torch.tensor(counts, dtype=torch.int64)).to(dtype)
+            w = self._weights[(kind, dtype)] = w.to(self.device)
+        return w
+
     def loss_weights(self, kind):
         """(V,) float32 per-vertex weight of the native mesh losses: "verts" 1 / (N V_m),
         "edges" 1 / (N E_m) (0 for a mesh without edges), m the vertex's mesh."""

@@ -17,6 +17,12 @@
     (NATIVE_MESHLOSS off) in the same process, and the native step replayed from a captured graph
     with a DeviceSeed.  `--sampling` runs (c) and (d) alone.
 
+(e) "point_mesh": point_mesh_face_distance and point_mesh_edge_distance, forward + backward to the
+    vertices and the points, 4 x sphere_642 against 5000 points each: kernels and copies of one call,
+    the device time of its kernels (their durations in a torch.profiler trace, summed; the native
+    kernels also one by one) and ms per call, on the native kernels and on the torch composition.
+    `--pointmesh` runs (e) alone.
+
     python tools/meshloss_bench.py --sweep [--out FILE]
 
 "chamfer_sweep": chamfer_distance forward alone and forward + backward at 5000 x 5000, 20000 x 20000
@@ -75,6 +81,56 @@ def count_launches(fn):
         ev = [e for e in json.load(open(tr))["traceEvents"] if e.get("ph") == "X"]
     return dict(kernels=sum(e.get("cat") == "kernel" for e in ev),
                 copies=sum(e.get("cat") in ("gpu_memcpy", "gpu_memset") for e in ev))
+
+
+def kernel_times(fn):
+    """(total device time of fn()'s kernels in us, {kernel name: us}) from a torch.profiler trace."""
+    from torch.profiler import ProfilerActivity, profile
+    with profile(activities=[ProfilerActivity.CPU, ProfilerActivity.CUDA]) as prof:
+        fn()
+        torch.cuda.synchronize()
+    with tempfile.TemporaryDirectory() as td:
+        tr = os.path.join(td, "t.json")
+        prof.export_chrome_trace(tr)
+        ev = [e for e in json.load(open(tr))["traceEvents"] if e.get("ph") == "X" and e.get("cat") == "kernel"]
+    per = {}
+    for e in ev:
+        name = e["name"].replace("(anonymous namespace)::", "").split("(")[0].split("<")[0].split("::")[-1].split(" ")[-1]
+        per[name] = round(per.get(name, 0.0) + float(e["dur"]), 2)
+    return round(sum(float(e["dur"]) for e in ev), 2), per
+
+
+def point_mesh(device, steps, repeats):
+    """point_mesh_face_distance / point_mesh_edge_distance, forward + backward, 4 x sphere_642 against
+    5000 points each (on a sphere a little larger than the meshes)."""
+    from pertrenderer_amd.renderer import Pointclouds
+    _, src, S = _sampling_shapes(device)[0]
+    N = len(src)
+    g = torch.Generator().manual_seed(S)
+    pts = (torch.nn.functional.normalize(torch.randn((N, S, 3), generator=g), dim=2) * 1.1 + 0.05).to(device)
+    pts.requires_grad_(True)
+    cloud = Pointclouds(pts)
+    d = torch.zeros((src.verts_packed().shape[0], 3), device=device, requires_grad=True)
+    rows = []
+    for name, fn in (("faces", L.point_mesh_face_distance), ("edges", L.point_mesh_edge_distance)):
+        def call():
+            d.grad = pts.grad = None
+            fn(src.offset_verts(d), cloud).backward()
+
+        def measure():
+            for _ in range(3):
+                call()
+            row = count_launches(call)
+            total, per = kernel_times(call)
+            row["kernel_us"] = total
+            if L.NATIVE_MESHLOSS:
+                row["native_kernels_us"] = {k: v for k, v in per.items()
+                                            if k.startswith(("prim_", "point", "vert_gather"))}
+            row["ms"] = spread(timed(call, steps, repeats))
+            return row
+
+        rows.append(dict(prims=name, shape="4xsphere_642", points_per_cloud=S, **_both_paths(measure)))
+    return rows
 
 
 def regulariser_step(device, steps, repeats):
@@ -281,6 +337,7 @@ def main():
     ap.add_argument("--out")
     ap.add_argument("--sweep", action="store_true", help="chamfer over PR_CHAMFER_SPLITS instead of (a) and (b)")
     ap.add_argument("--sampling", action="store_true", help="(c) and (d) only")
+    ap.add_argument("--pointmesh", action="store_true", help="(e) only")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         raise SystemExit("meshloss_bench needs a ROCm device: a CPU run gives no timing")
@@ -290,9 +347,12 @@ def main():
                    chamfer_sweep=chamfer_sweep(device, max(args.steps // 4, 10), min(args.repeats, 5)))
     elif args.sampling:
         res = dict(device=torch.cuda.get_device_name(0), **_sampling_run(device, args))
+    elif args.pointmesh:
+        res = dict(device=torch.cuda.get_device_name(0), point_mesh=point_mesh(device, max(args.steps // 10, 5), args.repeats))
     else:
         res = _default_run(device, args)
         res.update(_sampling_run(device, args))
+        res["point_mesh"] = point_mesh(device, max(args.steps // 10, 5), args.repeats)
     line = json.dumps(res)
     print(line)
     if args.out:
