@@ -762,6 +762,66 @@ size_t pr_point_mesh_workspace(int32_t prim, int64_t N, int64_t P, int64_t M, in
 int pr_point_mesh_fwd(const PRPointMeshArgs* args, void* stream);
 int pr_point_mesh_bwd(const PRPointMeshArgs* args, void* stream);
 
+/* Point-cloud rasterizer (PyTorch3D 0.4.0 rasterize_points; csrc/pr_points.hip; additive to ABI 21).
+ * points are packed NDC x, y with view-space z; cloud n owns [cloud_first[n], + cloud_count[n]) and is
+ * drawn into image n.  Pixel (row, col) has the mesh rasterizer's centre.  Point p is a candidate of
+ * a pixel when z_p >= 0 and d2 = (xf - x_p)^2 + (yf - y_p)^2 < r_p^2 (strict; NaN compares false);
+ * every pixel keeps the K candidates smallest in (z, packed index), ascending.  Unused slots hold -1.
+ * K <= PR_POINTS_MAX_K.  The backward gathers over the point -> fragment entries CSR (a stable sort
+ * of idx by the caller): no atomics. */
+#define PR_POINTS_MAX_K 64
+typedef struct {
+  const float* points;           /* (P,3) packed */
+  const int64_t* cloud_first;    /* (N); fwd */
+  const int64_t* cloud_count;    /* (N); fwd */
+  const float* radius;           /* (P) per-point radii in packed order, or NULL: radius_scalar; fwd */
+  float radius_scalar;
+  int32_t N, H, W, K;
+  int64_t P;
+  int64_t* idx;                  /* (N,H,W,K) packed point or -1: fwd out, bwd in */
+  float* zbuf;                   /* (N,H,W,K) fwd out */
+  float* dists;                  /* (N,H,W,K) fwd out */
+  const int64_t* point_start;    /* (P+1) point -> its entries e = ((n H + row) W + col) K + k, ascending; bwd */
+  const int64_t* point_entries;  /* (N H W K) */
+  const float* grad_zbuf;        /* (N,H,W,K) bwd in */
+  const float* grad_dists;       /* (N,H,W,K) bwd in */
+  float* grad_points;            /* (P,3) bwd out, overwritten */
+} PRPointsRastArgs;
+
+int pr_points_rast_fwd(const PRPointsRastArgs* args, void* stream);
+int pr_points_rast_bwd(const PRPointsRastArgs* args, void* stream);
+
+/* Point compositors (PyTorch3D 0.4.0 alpha_composite / norm_weighted_sum / weighted_sum) on the
+ * rasterizer's layouts: idx, alphas (N,H,W,K), features (P,C) rows, out (N,H,W,C).  Slots with
+ * idx outside [0, P) are skipped.  With a_k, f_k the alpha and feature row of valid slot k:
+ * alpha   out = sum_k a_k prod_{j<k valid}(1 - a_j) f_k
+ * norm    out = sum_k a_k f_k / max(sum_k a_k, 1e-4)
+ * weight  out = sum_k a_k f_k.
+ * The backward is the exact derivative (the alpha chain from prefix and suffix products, no
+ * division); d features gathers over the same CSR as pr_points_rast_bwd. */
+#define PR_POINTS_ALPHA 0
+#define PR_POINTS_NORM 1
+#define PR_POINTS_WEIGHTED 2
+typedef struct {
+  const int64_t* idx;            /* (N,H,W,K) */
+  const float* alphas;           /* (N,H,W,K) */
+  const float* features;         /* (P,C) */
+  int32_t N, H, W, K, C, mode;
+  int64_t P;
+  float* out;                    /* (N,H,W,C) fwd out */
+  void* workspace;               /* bwd: pr_points_workspace bytes */
+  size_t workspace_bytes;
+  const int64_t* point_start;    /* (P+1); bwd */
+  const int64_t* point_entries;  /* (N H W K); bwd */
+  const float* grad_out;         /* (N,H,W,C) bwd in */
+  float* grad_alphas;            /* (N,H,W,K) bwd out, overwritten */
+  float* grad_features;          /* (P,C) bwd out, overwritten */
+} PRPointsCompositeArgs;
+
+size_t pr_points_workspace(int32_t N, int32_t H, int32_t W, int32_t K);  /* bytes; 0 for sizes the entry points reject */
+int pr_points_composite_fwd(const PRPointsCompositeArgs* args, void* stream);
+int pr_points_composite_bwd(const PRPointsCompositeArgs* args, void* stream);
+
 int pr_abi_version(void);
 const char* pr_last_error(void);
 

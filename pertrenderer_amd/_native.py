@@ -203,6 +203,24 @@ class PRPointMeshArgs(C.Structure):
                 ("grad_verts", _vp)]
 
 
+PR_POINTS_MAX_K = 64  # the largest points_per_pixel pr_points_rast_fwd serves
+PR_POINTS_ALPHA, PR_POINTS_NORM, PR_POINTS_WEIGHTED = 0, 1, 2
+
+
+class PRPointsRastArgs(C.Structure):
+    _fields_ = [("points", _vp), ("cloud_first", _vp), ("cloud_count", _vp), ("radius", _vp),
+                ("radius_scalar", C.c_float), ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("K", C.c_int32),
+                ("P", C.c_int64), ("idx", _vp), ("zbuf", _vp), ("dists", _vp), ("point_start", _vp),
+                ("point_entries", _vp), ("grad_zbuf", _vp), ("grad_dists", _vp), ("grad_points", _vp)]
+
+
+class PRPointsCompositeArgs(C.Structure):
+    _fields_ = [("idx", _vp), ("alphas", _vp), ("features", _vp), ("N", C.c_int32), ("H", C.c_int32),
+                ("W", C.c_int32), ("K", C.c_int32), ("C", C.c_int32), ("mode", C.c_int32), ("P", C.c_int64),
+                ("out", _vp), ("workspace", _vp), ("workspace_bytes", C.c_size_t), ("point_start", _vp),
+                ("point_entries", _vp), ("grad_out", _vp), ("grad_alphas", _vp), ("grad_features", _vp)]
+
+
 # every symbol include/pertrender.h declares, with its argument struct (None = no args)
 EXPORTS = {
     "pr_abi_version": (C.c_int, []),
@@ -259,6 +277,11 @@ EXPORTS = {
     "pr_point_mesh_workspace": (C.c_size_t, [C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_int64]),
     "pr_point_mesh_fwd": (C.c_int, [C.POINTER(PRPointMeshArgs), _vp]),
     "pr_point_mesh_bwd": (C.c_int, [C.POINTER(PRPointMeshArgs), _vp]),
+    "pr_points_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32, C.c_int32]),
+    "pr_points_rast_fwd": (C.c_int, [C.POINTER(PRPointsRastArgs), _vp]),
+    "pr_points_rast_bwd": (C.c_int, [C.POINTER(PRPointsRastArgs), _vp]),
+    "pr_points_composite_fwd": (C.c_int, [C.POINTER(PRPointsCompositeArgs), _vp]),
+    "pr_points_composite_bwd": (C.c_int, [C.POINTER(PRPointsCompositeArgs), _vp]),
 }
 ABI_VERSION = 21
 

@@ -112,6 +112,16 @@ PR_HD int centre_out(int k, int n) { return (k & 1) ? n / 2 - 1 - (k >> 1) : n /
 // --------------------------------------------------------------------- math
 PR_DEV float heaviside1(float x) { return x >= 0.f ? 1.f : 0.f; }  // torch.heaviside(x, 1)
 
+// NDC coordinate of pixel-centre index i along an axis of S1 pixels (S2: the other axis), PyTorch3D's
+// non-square convention; pixel (row, col) has centre (ndc(W-1-col, W, H), ndc(H-1-row, H, W)).
+// Shared by the mesh rasterizer (pr_rast.hip) and the point rasterizer (pr_points.hip).
+PR_DEV float ndc(int i, int S1, int S2) {
+  float range = 2.0f;
+  if (S1 > S2) range = ((float)S1 * range) / (float)S2;
+  const float off = range / 2.0f;
+  return -off + (range * (float)i + off) / (float)S1;
+}
+
 
 template <typename T>
 PR_DEV T ld(const T* p) { return *p; }

@@ -90,13 +90,6 @@ PR_DEV float tri_dist2(V2 p, V2 v0, V2 v1, V2 v2) {
   return m < e12 ? m : e12;
 }
 
-PR_DEV float ndc(int i, int S1, int S2) {
-  float range = 2.0f;
-  if (S1 > S2) range = ((float)S1 * range) / (float)S2;
-  const float off = range / 2.0f;
-  return -off + (range * (float)i + off) / (float)S1;
-}
-
 // Per-face record for the forward traversal (96 B).  Besides the vertices it holds
 // the edge deltas and the (area + eps) that bary_fwd / seg_dist2 would compute:
 // the same IEEE operations on the same operands, so every per-pixel value below is

@@ -11,6 +11,9 @@ from .loss import (chamfer_distance, mesh_edge_loss, mesh_laplacian_smoothing, m
 from .mesh import Meshes, TexturesVertex
 from .ops import sample_points_from_meshes
 from .pointclouds import Pointclouds
+from .points import (AlphaCompositor, NormWeightedCompositor, PointFragments, PointsRasterizationSettings,
+                     PointsRasterizer, PointsRenderer, alpha_composite, norm_weighted_sum, rasterize_points,
+                     weighted_sum)
 from .rasterizer import Fragments, MeshRasterizer, RasterizationSettings, rasterize_meshes
 from .renderer import BlendParams, DirectionalLights, Materials, MeshRenderer, PointLights
 from .shaders import HardPhongShader, SoftPhongShader, SoftSilhouetteShader
@@ -29,4 +32,6 @@ __all__ = [
     "Pointclouds", "sample_points_from_meshes", "HardPhongShader", "SoftPhongShader",
     "SoftSilhouetteShader", "phong_shading", "Textures", "TexturesAtlas", "TexturesUV", "Rotate",
     "random_rotations", "so3_exp_map", "so3_exponential_map", "so3_log_map", "so3_relative_angle",
+    "AlphaCompositor", "NormWeightedCompositor", "PointFragments", "PointsRasterizationSettings", "PointsRasterizer",
+    "PointsRenderer", "alpha_composite", "norm_weighted_sum", "rasterize_points", "weighted_sum",
 ]

@@ -1,6 +1,7 @@
 """Point-cloud batch (the PyTorch3D ``Pointclouds`` subset the point-to-mesh losses of
-renderer/loss.py take): a list of (P_i,3) tensors, or a padded (N,P,3) tensor whose clouds all have
-P points.
+renderer/loss.py and the point renderer of renderer/points.py take): a list of (P_i,3) tensors, or a
+padded (N,P,3) tensor whose clouds all have P points, with optional normals and per-point features
+(C channels, the colours PointsRenderer composites) in the same two forms.
 
 The points are kept as given, so gradients flow to the caller's tensors through every view.  The
 index tables (points per cloud, first packed index, cloud of a packed point, the losses' per-point
@@ -12,7 +13,7 @@ import torch
 
 
 class Pointclouds:
-    def __init__(self, points, normals=None):
+    def __init__(self, points, normals=None, features=None):
         self._padded = None
         if torch.is_tensor(points):
             if points.dim() != 3 or points.shape[2] != 3:
@@ -37,6 +38,23 @@ class Pointclouds:
         if self._normals is not None and [tuple(n.shape) for n in self._normals] != [tuple(p.shape) for p in self._list]:
             raise ValueError("normals must have the shapes of points")
         self.npoints = [p.shape[0] for p in self._list]  # Python ints: no host read later
+        # per-point features (colours, ...) of C channels: a list of (P_i,C) or a padded (N,P,C) tensor
+        self._features_padded = None
+        if features is None:
+            self._features = None
+        elif torch.is_tensor(features):
+            if features.dim() != 3:
+                raise ValueError(f"features must be (N,P,C) or a list of (P_i,C), got {tuple(features.shape)}")
+            self._features_padded = features
+            self._features = [f for f in features]
+        else:
+            self._features = list(features)
+        if self._features is not None:
+            if (len(self._features) != len(self._list)
+                    or any(not torch.is_tensor(f) or f.dim() != 2 for f in self._features)
+                    or [f.shape[0] for f in self._features] != self.npoints
+                    or any(f.shape[1] != self._features[0].shape[1] for f in self._features)):
+                raise ValueError("features must have one (P_i,C) row block per cloud, with one C")
         self.device = self._list[0].device if self._list else torch.device("cpu")
         self._idx = None
         self._weights = {}
@@ -46,9 +64,11 @@ class Pointclouds:
 
     def to(self, device):
         if self._padded is not None:
-            return Pointclouds(self._padded.to(device), None if self._normals is None else self.normals_padded().to(device))
+            return Pointclouds(self._padded.to(device), None if self._normals is None else self.normals_padded().to(device),
+                               None if self._features is None else self.features_padded().to(device))
         return Pointclouds([p.to(device) for p in self._list],
-                           None if self._normals is None else [n.to(device) for n in self._normals])
+                           None if self._normals is None else [n.to(device) for n in self._normals],
+                           None if self._features is None else [f.to(device) for f in self._features])
 
     # ---------------------------------------------------------------- views
     def points_list(self):
@@ -73,6 +93,39 @@ class Pointclouds:
     def normals_padded(self):
         return None if self._normals is None else self._pad(self._normals, self._normals_padded)
 
+    def features_list(self):
+        return self._features
+
+    def features_packed(self):
+        """(P,C) rows in packed order (one point's channels are contiguous), or None."""
+        if self._features is None:
+            return None
+        if self._features_padded is not None:
+            return self._features_padded.reshape(-1, self._features_padded.shape[2])
+        return self._features[0] if len(self._features) == 1 else torch.cat(self._features, dim=0)
+
+    def features_padded(self):
+        return None if self._features is None else self._pad(self._features, self._features_padded)
+
+    def update_padded(self, new_points):
+        """A cloud batch with the points `new_points` (N,P,3) (P the longest cloud; rows past a cloud's
+        count are dropped) and this batch's features, normals and cached index tables."""
+        if not torch.is_tensor(new_points) or tuple(new_points.shape) != (len(self._list), max(self.npoints, default=0), 3):
+            raise ValueError(f"new_points must be ({len(self._list)},{max(self.npoints, default=0)},3)")
+        if self._padded is not None:
+            return self._with_points(new_points)
+        return self._with_points([new_points[i, :n] for i, n in enumerate(self.npoints)])
+
+    def _with_points(self, points):
+        """This batch with other points of the same sizes (a padded tensor or a list)."""
+        new = Pointclouds(points)
+        if new.npoints != self.npoints:
+            raise ValueError(f"the new points must have {self.npoints} rows per cloud, got {new.npoints}")
+        new._normals, new._normals_padded = self._normals, self._normals_padded
+        new._features, new._features_padded = self._features, self._features_padded
+        new._idx, new._weights = self._idx, self._weights
+        return new
+
     def _pad(self, items, padded):
         if padded is not None:
             return padded
@@ -80,7 +133,7 @@ class Pointclouds:
             return items[0][None]  # a view: no copy kernel
         if all(n == self.npoints[0] for n in self.npoints):
             return torch.stack(items, 0)
-        out = items[0].new_zeros((len(items), max(self.npoints), 3))
+        out = items[0].new_zeros((len(items), max(self.npoints), items[0].shape[1]))
         for i, p in enumerate(items):
             out[i, : p.shape[0]] = p
         return out

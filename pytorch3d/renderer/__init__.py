@@ -7,3 +7,6 @@ from pertrenderer_amd.renderer import (BlendParams, DirectionalLights, FoVPerspe
                                        look_at_rotation, look_at_view_transform, rasterize_meshes,
                                        sigmoid_alpha_blend, softmax_rgb_blend)
 from pertrenderer_amd.renderer.rasterizer import Fragments  # noqa: F401
+from pertrenderer_amd.renderer.points import (AlphaCompositor, NormWeightedCompositor, PointFragments,  # noqa: F401
+                                              PointsRasterizationSettings, PointsRasterizer, PointsRenderer,
+                                              alpha_composite, norm_weighted_sum, rasterize_points, weighted_sum)
