@@ -69,8 +69,7 @@ PR_DEV int64_t cloud_len(const int64_t* len, int64_t n, int64_t full) {
 }
 
 PR_DEV void consider(float qx, float qy, float qz, float px, float py, float pz, int32_t j, float& best, int32_t& arg) {
-  const float dx = qx - px, dy = qy - py, dz = qz - pz;
-  const float d = dx * dx + dy * dy + dz * dz;
+  const float d = dist2_3(qx, qy, qz, px, py, pz);
   if (d < best) {
     best = d;
     arg = j;

@@ -122,6 +122,13 @@ PR_DEV float ndc(int i, int S1, int S2) {
   return -off + (range * (float)i + off) / (float)S1;
 }
 
+// Squared distance of two 3-D points: the squared coordinate differences summed in coordinate
+// order, so a point on top of another gives exactly 0.  The one d^2 of the nearest-neighbour
+// searches (pr_chamfer.hip); renderer/ops.py's knn_points forms the same sum in torch.
+PR_DEV float dist2_3(float qx, float qy, float qz, float px, float py, float pz) {
+  const float dx = qx - px, dy = qy - py, dz = qz - pz;
+  return dx * dx + dy * dy + dz * dz;
+}
 
 template <typename T>
 PR_DEV T ld(const T* p) { return *p; }

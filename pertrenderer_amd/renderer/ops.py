@@ -9,7 +9,12 @@ The per-mesh face tables are read on the device and the backward's face -> sampl
 device sort, so after one call on a topology a call builds nothing on the host and does not
 synchronise: the deformation step can be captured in a HIP graph.  PR_NATIVE_MESHLOSS=0 (or
 loss.NATIVE_MESHLOSS = False), CPU tensors and other dtypes take the torch composition of the same
-formulas (_sample_points_torch).  Parity with PyTorch3D is unpinned (not installable here)."""
+formulas (_sample_points_torch).  Parity with PyTorch3D is unpinned (not installable here).
+
+``knn_points`` / ``knn_gather`` (PyTorch3D 0.4.0, same module) are here as torch compositions on every
+device: chunked over the queries, a stable lowest-index tie rule, lengths read on the device."""
+import collections
+
 import torch
 
 from .. import noise as _noise
@@ -228,3 +233,129 @@ def sample_points_from_meshes(meshes, num_samples=10000, return_normals=False, *
             uniforms = _philox_uniforms(seed, N, S, v.device)
         samples, normals = _sample_points_torch(meshes, uniforms, bool(return_normals))[:2]
     return (samples, normals) if return_normals else samples
+
+
+# ------------------------------------------------------------------ K nearest neighbours
+_KNN = collections.namedtuple("_KNN", "dists idx knn")
+_TORCH_CHUNK = 1 << 22  # entries of the (queries, P2) d^2 block the torch composition holds at once
+
+
+def _check_knn_inputs(p1, p2, lengths1, lengths2, K):
+    if not torch.is_tensor(p1) or not torch.is_tensor(p2) or p1.dim() != 3 or p2.dim() != 3:
+        raise ValueError("expected p1 (N,P1,D) and p2 (N,P2,D) tensors, got "
+                         f"{tuple(p1.shape) if torch.is_tensor(p1) else type(p1).__name__} and "
+                         f"{tuple(p2.shape) if torch.is_tensor(p2) else type(p2).__name__}")
+    if not p1.is_floating_point() or p1.dtype != p2.dtype:
+        raise ValueError(f"p1 and p2 must be floating point of one dtype, got {p1.dtype} and {p2.dtype}")
+    if p1.device != p2.device:
+        raise ValueError(f"p1 is on {p1.device}, p2 on {p2.device}")
+    if p1.shape[0] != p2.shape[0] or p1.shape[2] != p2.shape[2]:
+        raise ValueError(f"p1 and p2 must agree in N and D, got {tuple(p1.shape)} and {tuple(p2.shape)}")
+    if isinstance(K, bool) or not isinstance(K, int) or K < 1:
+        raise ValueError(f"K must be an int >= 1, got {K!r}")
+    for t, name in ((lengths1, "lengths1"), (lengths2, "lengths2")):
+        if t is None:
+            continue
+        if not torch.is_tensor(t) or tuple(t.shape) != (p1.shape[0],) or t.is_floating_point() or t.is_complex() \
+                or t.dtype == torch.bool:
+            raise ValueError(f"{name} must be an integer tensor of shape ({p1.shape[0]},), got "
+                             f"{(t.dtype, tuple(t.shape)) if torch.is_tensor(t) else type(t).__name__}")
+        if t.device != p1.device:
+            raise ValueError(f"{name} is on {t.device}, p1 on {p1.device}")
+
+
+def _knn_points_torch(p1, p2, lengths1=None, lengths2=None, K=1):
+    """knn_points in torch ops, in the inputs' dtype: (dists (N,P1,K), idx (N,P1,K) int64, -1
+    where a slot holds no neighbour).  Per cloud and per chunk of queries (no (N,P1,P2) tensor):
+    d^2 summed coordinate by coordinate, NaN and padded columns at +inf, the K smallest by topk's
+    kth value with the lowest indices among the entries equal to it, then a stable sort of those K
+    (the lowest index first on equal d^2; topk's tie order is not relied on).  The distances are then
+    formed again from the chosen points, which is what autograd differentiates; the lengths are
+    read on the device."""
+    N, P1, D = p1.shape
+    P2, Kc = p2.shape[1], min(K, p2.shape[1])
+    dev, inf = p1.device, float("inf")
+    with torch.no_grad():
+        l1 = torch.full((N,), P1, dtype=torch.int64, device=dev) if lengths1 is None else lengths1.to(torch.int64).clamp(0, P1)
+        l2 = torch.full((N,), P2, dtype=torch.int64, device=dev) if lengths2 is None else lengths2.to(torch.int64).clamp(0, P2)
+        idx = torch.full((N, P1, K), -1, dtype=torch.int64, device=dev)
+        cols = torch.arange(P2, device=dev)
+        step = max(1, _TORCH_CHUNK // max(P2, 1))
+        for n in range(N if Kc > 0 else 0):
+            dead = (cols >= l2[n])[None, :]
+            for c0 in range(0, P1, step):
+                q = p1[n, c0:c0 + step]
+                d = torch.zeros((q.shape[0], P2), dtype=p1.dtype, device=dev)
+                for c in range(D):
+                    diff = q[:, c, None] - p2[n, None, :, c]
+                    d = d + diff * diff
+                d = torch.where(dead | torch.isnan(d), inf, d)
+                # the K smallest under (d^2, index) without sorting the row: topk gives the kth value t
+                # (its choice among equal values is not used); everything below t is in, and of the
+                # entries equal to t the lowest indices fill the rest
+                t = torch.topk(d, Kc, dim=1, largest=False).values[:, -1:]
+                below, equal = d < t, d == t
+                chosen = below | (equal & (equal.cumsum(1) <= Kc - below.sum(1, keepdim=True)))
+                # exactly Kc per row; their indices in ascending order, as the Kc largest of P2 - j
+                j = P2 - torch.topk(torch.where(chosen, P2 - cols, 0), Kc, dim=1).values
+                val, order = torch.sort(d.gather(1, j), dim=1, stable=True)  # ascending index within equal d^2
+                j = j.gather(1, order)
+                idx[n, c0:c0 + step, :Kc] = torch.where(val < inf, j, -1)
+        slot = torch.arange(K, device=dev)[None, None, :] < l2.clamp(max=K)[:, None, None]
+        live = (torch.arange(P1, device=dev)[None, :] < l1[:, None])[:, :, None] & slot
+        idx = torch.where(live, idx, -1)
+        found = idx >= 0
+        miss = torch.where(torch.isnan(p1).any(dim=2, keepdim=True), float("nan"), inf).to(p1.dtype).expand(N, P1, K)
+        fill = torch.where(live, miss, torch.zeros((), dtype=p1.dtype, device=dev))
+    near = p2[torch.arange(N, device=dev)[:, None, None], idx.clamp(min=0)]  # (N,P1,K,D), indexed: see loss._normal_terms
+    diff = (p1[:, :, None, :] - near).masked_fill(~found[..., None], 0.0)
+    d = torch.zeros((N, P1, K), dtype=p1.dtype, device=dev)
+    for c in range(D):
+        d = d + diff[..., c] * diff[..., c]
+    return torch.where(found, d, fill), idx
+
+
+def knn_gather(x, idx, lengths=None):
+    """out[n,l,k] = x[n, idx[n,l,k]] for x (N,M,U) and idx (N,L,K): (N,L,K,U) (PyTorch3D 0.4.0
+    knn_gather).  With lengths (N,), the slots k >= lengths[n] are zero.  Torch index ops on the
+    device, no host read; the backward is autograd's index backward."""
+    if not torch.is_tensor(x) or not torch.is_tensor(idx) or x.dim() != 3 or idx.dim() != 3 or x.shape[0] != idx.shape[0]:
+        raise ValueError("expected x (N,M,U) and idx (N,L,K)")
+    if idx.is_floating_point() or idx.dtype == torch.bool:
+        raise ValueError(f"idx must be an integer tensor, got {idx.dtype}")
+    N, K = idx.shape[0], idx.shape[2]
+    out = x[torch.arange(N, device=x.device)[:, None, None], idx.to(torch.int64)]
+    if lengths is not None:
+        if not torch.is_tensor(lengths) or tuple(lengths.shape) != (N,) or lengths.is_floating_point() or lengths.dtype == torch.bool:
+            raise ValueError(f"lengths must be an integer tensor of shape ({N},)")
+        pad = torch.arange(K, device=x.device)[None, None, :] >= lengths.to(x.device)[:, None, None]
+        out = out.masked_fill(pad.expand(idx.shape)[..., None], 0.0)
+    return out
+
+
+def knn_points(p1, p2, lengths1=None, lengths2=None, K=1, version=-1, return_nn=False, return_sorted=True):
+    """The K nearest neighbours in p2 (N,P2,D) of every point of p1 (N,P1,D) (PyTorch3D 0.4.0
+    knn_points): a namedtuple (dists (N,P1,K), idx (N,P1,K) int64, knn (N,P1,K,D) or None).
+
+    dists are the squared Euclidean distances, ascending; neighbours are ordered by (d^2, index), so
+    equal distances come out lowest index first.  d^2 is the sum over the coordinates, in order, of
+    the squared differences: a point on top of its neighbour gives exactly 0.  lengths1 / lengths2
+    (N,) integer tensors give the clouds' lengths (read on the device, clamped to [0, P]); rows
+    i >= lengths1[n] and slots k >= min(K, lengths2[n]) have dists 0 and idx 0 (_knn_points_torch's
+    own idx holds -1 there, and the gradient skips such entries).  K > P2 is allowed.  A NaN database
+    point is never chosen; a live slot that finds no neighbour below +inf gets NaN if its query is
+    NaN, else +inf, and no gradient.  dists is differentiable in p1 and p2, and so is knn
+    (return_nn=True: knn_gather(p2, idx, lengths2)).  `version` (-1..3) is accepted and ignored, and
+    return_sorted=False still returns the sorted order.
+
+    Every device and dtype takes the torch composition of these formulas (_knn_points_torch): per
+    cloud and per chunk of queries, so no (N,P1,P2) tensor is held at once, with no host read of the
+    lengths in the forward; capture in a HIP graph is untested.  There is no native kernel for this
+    op yet.  Arguments are checked (ValueError) before
+    anything is launched.  Parity with PyTorch3D is unpinned (not installable here)."""
+    _check_knn_inputs(p1, p2, lengths1, lengths2, K)
+    if isinstance(version, bool) or not isinstance(version, int) or not -1 <= version <= 3:
+        raise ValueError(f"version must be an int in -1..3, got {version!r}")
+    dists, raw = _knn_points_torch(p1, p2, lengths1, lengths2, K)
+    idx = raw.clamp(min=0)
+    return _KNN(dists, idx, knn_gather(p2, idx, lengths2) if return_nn else None)
