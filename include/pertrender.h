@@ -44,6 +44,9 @@
  *   pr_point_mesh_fwd / _bwd
  *       PyTorch3D 0.4.0 point_mesh_face_distance / point_mesh_edge_distance, the losses that fit
  *       a mesh to a point cloud directly.
+ *   pr_align_fwd, pr_icp_run
+ *       PyTorch3D 0.4.0 corresponding_points_alignment / iterative_closest_point, which put a
+ *       scanned cloud into the mesh's frame before those losses.
  */
 #ifndef PERTRENDER_H_
 #define PERTRENDER_H_
@@ -821,6 +824,85 @@ typedef struct {
 size_t pr_points_workspace(int32_t N, int32_t H, int32_t W, int32_t K);  /* bytes; 0 for sizes the entry points reject */
 int pr_points_composite_fwd(const PRPointsCompositeArgs* args, void* stream);
 int pr_points_composite_bwd(const PRPointsCompositeArgs* args, void* stream);
+
+/* Rigid / similarity alignment of point clouds (PyTorch3D 0.4.0 corresponding_points_alignment and
+ * iterative_closest_point), float32 points, D = 3, row vectors: x R ~ y.  Additive to ABI 21.
+ * A transform is PR_ICP_STATE floats per cloud: R row-major (9), T (3), s.
+ *   pr_align_fwd: with w the weights (1 on the rows below x_len[n] when `weights` is NULL; rows at or
+ *     past the length are not read), Xmu = sum w x / max(sum w, eps), Ymu likewise, xc = x - Xmu,
+ *     C = sum w^2 xc^T (y - Ymu) / total, total = max(sum w, eps) with weights and max(x_len, 1)
+ *     without; U S V^T = C by cyclic one-sided Jacobi in float64 (singular values descending);
+ *     E = diag(1, 1, det(U V^T)) unless allow_reflection; R = U E V^T;
+ *     s = (diag(E) . S) / max(sum w^2 |xc|^2 / total, eps) with estimate_scale, else 1;
+ *     T = Ymu - s Xmu R.  All sums are float64, per workgroup in a fixed order and the workgroups'
+ *     records in index order: no atomics, the same bits on every call.  A non-finite moment makes
+ *     that cloud's R, T and s NaN.
+ *   pr_icp_run: `iterations` ICP iterations enqueued on the stream with no host read.  An iteration:
+ *     Xt_i = s (x_i R) + T from `state` (formed in registers), the nearest point of y below
+ *     y_len[n] to every Xt_i (d^2 = the squared coordinate differences summed in order, the lowest
+ *     index on equal d^2, NaN points never chosen; the database is cut into ranges over a further
+ *     grid dimension when the queries alone would leave the device idle, PR_ICP_SPLITS overrides the
+ *     count, read per call), pr_align_fwd's solve of the initial x against those neighbours with the
+ *     rows below x_len[n] as weights, and rmse = sqrt(mean |Xt'_i - nn_i|^2) of the new transform
+ *     against the same neighbours (closed form from the centred moments).  The transform goes to
+ *     `state` and to row `it` of `history`, it = flags[1], which is then incremented; flags[0] is
+ *     set when it > 0 and (prev - rmse) / prev <= relative_rmse_thr (float32) for every cloud.
+ *     Every kernel of an iteration returns at once when flags[0] is set or flags[1] has reached
+ *     max_iterations, so iterations may be enqueued in batches of any size with the same result.
+ *     A live query without a neighbour (NaN query, empty y cloud) makes its cloud's R, T, s and rmse
+ *     NaN.  phase & PR_ICP_BEGIN: before the iterations, flags are zeroed and the centroids of x
+ *     formed (the first call of a run; `state` holds the initial transform).  phase & PR_ICP_END:
+ *     after them, xt = s (x R) + T of `state` for all P rows. */
+#define PR_ICP_STATE 13
+#define PR_ICP_BEGIN 1
+#define PR_ICP_END 2
+typedef struct PRAlignArgs {
+  const float* x;            /* (N,P,3) */
+  const float* y;            /* (N,P,3) y_i corresponds to x_i */
+  const float* weights;      /* (N,P) or NULL */
+  const int64_t* x_len;      /* (N) or NULL: full length */
+  int64_t N, P;
+  int32_t estimate_scale, allow_reflection;
+  double eps;
+  float* R;                  /* (N,3,3) out */
+  float* T;                  /* (N,3) out */
+  float* s;                  /* (N) out */
+  void* workspace;           /* pr_align_workspace bytes */
+  size_t workspace_bytes;
+} PRAlignArgs;
+
+typedef struct PRIcpArgs {
+  const float* x;            /* (N,P,3) the initial clouds */
+  const float* y;            /* (N,Q,3) */
+  const int64_t* x_len;      /* (N) or NULL */
+  const int64_t* y_len;      /* (N) or NULL */
+  int64_t N, P, Q;
+  int32_t max_iterations, estimate_scale, allow_reflection, phase;
+  float relative_rmse_thr;
+  int32_t pad0;
+  float* state;              /* (N,PR_ICP_STATE) in: the initial transform, out: the last one */
+  float* history;            /* (max_iterations,N,PR_ICP_STATE) */
+  float* rmse;               /* (N) of the last executed iteration */
+  int32_t* idx;              /* (N,P) neighbours of the last executed iteration, -1: none / padding */
+  int32_t* idx_history;      /* (max_iterations,N,P) or NULL */
+  int32_t* flags;            /* [0] converged, [1] executed iterations */
+  float* xt;                 /* (N,P,3); written with PR_ICP_END */
+  void* workspace;           /* pr_icp_workspace bytes, the same buffer for every call of a run */
+  size_t workspace_bytes;
+} PRIcpArgs;
+
+/* Host only, no launch: the solve the kernels run on one cloud's summed record (tests pin the Jacobi
+ * SVD and the closed-form rmse without a device).  With c = Xmu, xc = x - Xmu, d = y - c, the record is
+ * PR_ALIGN_RECORD doubles: sum w, sum w d (3), sum w^2 xc (x) d (9, row-major), sum w^2 |xc|^2,
+ * sum w |d|^2, sum w^2 xc (3); xmu is (Xmu, sum w).  out: R (9), T (3), s, rmse (14 doubles; rmse is
+ * that of ICP, meaningful for 0 / 1 weights). */
+#define PR_ALIGN_RECORD 18
+int pr_align_solve_host(const double* record, const double* xmu, int32_t weighted, double eps, int32_t estimate_scale,
+                        int32_t allow_reflection, double* out);
+size_t pr_align_workspace(int64_t N, int64_t P);           /* bytes; 0 for sizes the entry point rejects */
+int pr_align_fwd(const PRAlignArgs* args, void* stream);
+size_t pr_icp_workspace(int64_t N, int64_t P, int64_t Q);  /* bytes; 0 for sizes the entry point rejects */
+int pr_icp_run(const PRIcpArgs* args, int32_t iterations, void* stream);
 
 int pr_abi_version(void);
 const char* pr_last_error(void);

@@ -221,6 +221,25 @@ class PRPointsCompositeArgs(C.Structure):
                 ("point_entries", _vp), ("grad_out", _vp), ("grad_alphas", _vp), ("grad_features", _vp)]
 
 
+PR_ICP_STATE = 13  # floats per cloud of a transform: R row-major (9), T (3), s
+PR_ICP_BEGIN, PR_ICP_END = 1, 2
+PR_ALIGN_RECORD = 18  # doubles of a cloud's moment record (pr_align_solve_host)
+
+
+class PRAlignArgs(C.Structure):
+    _fields_ = [("x", _vp), ("y", _vp), ("weights", _vp), ("x_len", _vp), ("N", C.c_int64), ("P", C.c_int64),
+                ("estimate_scale", C.c_int32), ("allow_reflection", C.c_int32), ("eps", C.c_double), ("R", _vp),
+                ("T", _vp), ("s", _vp), ("workspace", _vp), ("workspace_bytes", C.c_size_t)]
+
+
+class PRIcpArgs(C.Structure):
+    _fields_ = [("x", _vp), ("y", _vp), ("x_len", _vp), ("y_len", _vp), ("N", C.c_int64), ("P", C.c_int64),
+                ("Q", C.c_int64), ("max_iterations", C.c_int32), ("estimate_scale", C.c_int32),
+                ("allow_reflection", C.c_int32), ("phase", C.c_int32), ("relative_rmse_thr", C.c_float),
+                ("pad0", C.c_int32), ("state", _vp), ("history", _vp), ("rmse", _vp), ("idx", _vp), ("idx_history", _vp),
+                ("flags", _vp), ("xt", _vp), ("workspace", _vp), ("workspace_bytes", C.c_size_t)]
+
+
 # every symbol include/pertrender.h declares, with its argument struct (None = no args)
 EXPORTS = {
     "pr_abi_version": (C.c_int, []),
@@ -282,6 +301,12 @@ EXPORTS = {
     "pr_points_rast_bwd": (C.c_int, [C.POINTER(PRPointsRastArgs), _vp]),
     "pr_points_composite_fwd": (C.c_int, [C.POINTER(PRPointsCompositeArgs), _vp]),
     "pr_points_composite_bwd": (C.c_int, [C.POINTER(PRPointsCompositeArgs), _vp]),
+    "pr_align_solve_host": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.c_int32, C.c_double, C.c_int32,
+                                      C.c_int32, C.POINTER(C.c_double)]),
+    "pr_align_workspace": (C.c_size_t, [C.c_int64, C.c_int64]),
+    "pr_align_fwd": (C.c_int, [C.POINTER(PRAlignArgs), _vp]),
+    "pr_icp_workspace": (C.c_size_t, [C.c_int64, C.c_int64, C.c_int64]),
+    "pr_icp_run": (C.c_int, [C.POINTER(PRIcpArgs), C.c_int32, _vp]),
 }
 ABI_VERSION = 21
 

@@ -3,6 +3,8 @@ the native gfx950 kernels.  Only what the reference's hot path and its caller
 (experiments/eval.py) touch."""
 from .cameras import (FoVPerspectiveCameras, OpenGLPerspectiveCameras, camera_position_from_spherical_angles,
                       look_at_rotation, look_at_view_transform)
+from .alignment import (ICPSolution, SimilarityTransform, corresponding_points_alignment,
+                        iterative_closest_point)
 from .blending import hard_rgb_blend, sigmoid_alpha_blend, softmax_rgb_blend
 from .interp import interpolate_face_attributes
 from .io import load_obj, load_objs_as_meshes
@@ -34,4 +36,5 @@ __all__ = [
     "random_rotations", "so3_exp_map", "so3_exponential_map", "so3_log_map", "so3_relative_angle",
     "AlphaCompositor", "NormWeightedCompositor", "PointFragments", "PointsRasterizationSettings", "PointsRasterizer",
     "PointsRenderer", "alpha_composite", "norm_weighted_sum", "rasterize_points", "weighted_sum",
+    "ICPSolution", "SimilarityTransform", "corresponding_points_alignment", "iterative_closest_point",
 ]
