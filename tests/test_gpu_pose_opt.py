@@ -9,7 +9,8 @@ import numpy as np
 import pytest
 import torch
 
-from pertrenderer_amd import pose_opt
+import pose_cases as pc
+from pertrenderer_amd import host_layer, pose_opt
 from pertrenderer_amd.results import compare_pose_results
 
 pytestmark = pytest.mark.gpu
@@ -306,3 +307,229 @@ def test_pose_step_adam_matches_torch_adam(device):
     torch.testing.assert_close(m, ost["exp_avg"], rtol=1e-6, atol=1e-8)
     torch.testing.assert_close(s2, ost["exp_avg_sq"], rtol=1e-6, atol=1e-10)
     assert float(step) == float(ost["step"]) == 5.0
+
+
+# ---- float64 parity at launch and branch edges (tests/pose_cases.py)
+@pytest.fixture(params=pc.LAYERS)
+def layer(request):
+    with pc.autograd_layer(request.param) as ok:
+        if not ok:
+            pytest.skip(f"C++ autograd layer not built: {host_layer.error()}")
+        yield request.param
+
+
+def _mse_case(name):
+    """(img, target) float32 numpy: the shapes of the rgb_mse launch edges."""
+    rng = np.random.RandomState(31)
+    if name == "late-blocks":  # 768 tiles on 512 workgroups; only partials 256..511 are non-zero
+        return pc.mse_late_block_case()[:2]
+    shape, tshape = {"768-tiles": ((3, 256, 256, 4), (256, 256, 3)),  # grid-stride, two finalize rounds, random data
+                     "512-blocks": ((2, 256, 256, 3), (2, 256, 256, 3)),  # exactly 512 workgroups, batched target
+                     "one-pixel": ((1, 1, 1, 3), (1, 1, 3)),
+                     "five-channels": ((2, 16, 16, 5), (16, 16, 3))}[name]
+    return rng.rand(*shape).astype(np.float32), rng.rand(*tshape).astype(np.float32)
+
+
+@pytest.mark.parametrize("gscale", [1.0, 3.0])
+@pytest.mark.parametrize("name", ["late-blocks", "768-tiles", "512-blocks", "one-pixel", "five-channels"])
+def test_rgb_mse_matches_float64(name, gscale, layer, device):
+    """pose_opt.rgb_mse against the float64 value (1e-6 relative) and image gradient (1e-6 relative,
+    1e-9 absolute), twice with bitwise equal losses (fixed-order sums)."""
+    img_np, t_np = _mse_case(name)
+    ref, gref = pc.rgb_mse_ref(img_np, t_np, gscale)
+    assert ref > 0
+    t = torch.from_numpy(t_np).to(device)
+    losses = []
+    for _ in range(2):
+        img = torch.from_numpy(img_np).to(device).requires_grad_(True)
+        out = pose_opt.rgb_mse(img, t)
+        (g,) = torch.autograd.grad(out * gscale, img)
+        losses.append(out.detach().clone())
+    assert torch.equal(losses[0], losses[1])
+    print(name, "loss", float(out), "ref", ref)
+    assert abs(float(out) - ref) <= 1e-6 * abs(ref)
+    np.testing.assert_allclose(g.cpu().numpy().astype(np.float64), gref, rtol=1e-6, atol=1e-9)
+    if img_np.shape[-1] > 3:
+        assert float(g[..., 3:].abs().max()) == 0.0
+    if name == "late-blocks":
+        assert abs(ref - 1.0 / 3.0) < 1e-15
+
+
+class _PoseStep:
+    """The device buffers of pr_pose_step and their host mirror for pose_cases.pose_step_ref."""
+
+    def __init__(self, device, n, it=4, niter=8, best_loss=0.5, seed=12345):
+        self.f32 = dict(dtype=torch.float32, device=device)
+        self.n, self.niter = n, niter
+        g = torch.Generator().manual_seed(n)
+        self.t = dict(it=torch.tensor(it, dtype=torch.int64, device=device), losses=torch.zeros(niter, **self.f32),
+                      gnorms=torch.zeros(niter, **self.f32), best_loss=torch.tensor(best_loss, **self.f32),
+                      best=torch.randn(n, generator=g).to(device), v=torch.tensor([0.1, -0.2, 0.3], **self.f32),
+                      acc=torch.tensor([1.0, 2.0, 3.0], **self.f32), exp_avg=torch.zeros(n, **self.f32),
+                      exp_avg_sq=torch.zeros(n, **self.f32), step=torch.zeros((), **self.f32))
+        self.lr = torch.tensor(5e-2, **self.f32)
+        self.seed_value = seed
+        self.seed = None if seed is None else torch.tensor([seed], dtype=torch.int64, device=device)
+
+    def host(self, use_acc=True):
+        st = {k: (int(v) if k == "it" else v.cpu().numpy().copy()) for k, v in self.t.items()}
+        if not use_acc:
+            st["acc"] = None
+        return st
+
+    def call(self, loss, log_rot, grad, leaf=(None, None, None), post=False, use_acc=True, adam=False):
+        """Runs the kernel on the device buffers (log_rot and grad are updated in place) and the
+        restatement on their host copies: (state', log_rot', grad') of the restatement."""
+        from pertrenderer_amd import _native as nat
+        inputs = dict(loss=float(loss), log_rot=log_rot.cpu().numpy(), grad=grad.cpu().numpy()[: self.n], niter=self.niter,
+                      leaf=[None if x is None else float(x) for x in leaf], post=post, seed=self.seed_value, adam=adam,
+                      lr=float(self.lr))
+        ref = pc.pose_step_ref(self.host(use_acc), inputs)
+        a = nat.PRPoseStepArgs()
+        a.loss, a.log_rot, a.grad, a.it = nat.ptr(loss), nat.ptr(log_rot), nat.ptr(grad), nat.ptr(self.t["it"])
+        a.losses, a.gnorms, a.best_loss, a.best = (nat.ptr(self.t[k]) for k in ("losses", "gnorms", "best_loss", "best"))
+        a.v, a.acc, a.seed = nat.ptr(self.t["v"]), (nat.ptr(self.t["acc"]) if use_acc else None), nat.ptr(self.seed)
+        for i in range(3):
+            a.leaf_grad[i] = nat.ptr(leaf[i])
+        if adam:
+            a.exp_avg, a.exp_avg_sq, a.step, a.lr = (nat.ptr(x) for x in (self.t["exp_avg"], self.t["exp_avg_sq"],
+                                                                            self.t["step"], self.lr))
+        a.niter, a.n, a.post, a.adam = self.niter, self.n, int(post), int(adam)
+        nat.call("pr_pose_step", "pose_step", loss, a)
+        torch.cuda.synchronize()
+        return ref
+
+    def assert_bookkeeping(self, ref_state):
+        """Records, best pose, running sums, EMA and counter: bitwise the float32 restatement's."""
+        now = self.host()
+        for k in ("it", "losses", "gnorms", "best_loss", "best", "v", "acc"):
+            if ref_state[k] is not None:
+                assert np.array_equal(now[k], ref_state[k], equal_nan=True), (k, now[k], ref_state[k])
+
+
+def _f32(device, x):
+    return torch.tensor(x, dtype=torch.float32, device=device)
+
+
+@pytest.mark.parametrize("n", [6, 64])
+def test_pose_step_guard_draws_match_philox_ref(n, device):
+    """The guard's replacement gradient is 1e-5 * Box-Muller of Philox4x32-10 with counter
+    (t, t >> 32, i, "pose") and key seed ^ "guard_po" (oracle/philox_ref.py), for a full row of 64,
+    a partial last group (n = 6), another iteration and a missing seed."""
+    got = {}
+    for seed, it in ((12345, 4), (12345, 5), (None, 4)):
+        ps = _PoseStep(device, n, it=it, seed=seed)
+        grad = torch.full((n + 2,), -7.0, device=device)  # two sentinels past the row
+        grad[:n] = 0.0
+        grad[0] = 3000.0
+        log_rot = torch.linspace(-1, 1, n, device=device)
+        st, lr, gr = ps.call(_f32(device, 0.75), log_rot, grad, leaf=[_f32(device, x) for x in (0.5, -1.0, 2.0)], post=True)
+        ps.assert_bookkeeping(st)
+        assert float(ps.t["gnorms"][it]) == 3000.0 and int(ps.t["it"]) == it + 1
+        d = pc.guard_draws(seed, it, n)
+        g = grad.cpu().numpy().astype(np.float64)
+        assert (np.abs(g[:n] - d) <= pc.guard_tol(d)).all(), (seed, it, np.abs(g[:n] - d).max())
+        assert np.array_equal(g[n:], [-7.0, -7.0])
+        assert torch.equal(log_rot, torch.linspace(-1, 1, n, device=device))  # no Adam: the pose stays
+        got[(seed, it)] = g[:n]
+    assert np.abs(got[(12345, 4)] - got[(12345, 5)]).min() > 0 and np.abs(got[(12345, 4)] - got[(None, 4)]).min() > 0
+
+
+def test_pose_step_guard_threshold_is_strict(device):
+    nxt = float(np.nextafter(np.float32(1000), np.float32(np.inf)))
+    for first, replaced in ((1000.0, False), (nxt, True)):
+        ps = _PoseStep(device, 3)
+        grad = _f32(device, [first, 0.0, 0.0])
+        st, lr, gr = ps.call(_f32(device, 0.75), _f32(device, [0.1, 0.2, 0.3]), grad)
+        ps.assert_bookkeeping(st)
+        assert (float(ps.t["gnorms"][4]) > 1000.0) == replaced
+        if replaced:
+            d = pc.guard_draws(12345, 4, 3)
+            assert (np.abs(grad.cpu().numpy() - d) <= pc.guard_tol(d)).all()
+        else:
+            assert torch.equal(grad, _f32(device, [1000.0, 0.0, 0.0])) and float(ps.t["gnorms"][4]) == 1000.0
+
+
+def test_pose_step_equal_and_nan_losses_keep_the_best_pose(device):
+    ps = _PoseStep(device, 3, best_loss=0.5)
+    best0 = ps.t["best"].clone()
+    log_rot, grad = _f32(device, [0.1, 0.2, 0.3]), _f32(device, [3.0, 4.0, 0.0])
+    st, _, _ = ps.call(_f32(device, 0.5), log_rot, grad)  # loss == best_loss: the compare is strict
+    ps.assert_bookkeeping(st)
+    assert torch.equal(ps.t["best"], best0) and float(ps.t["best_loss"]) == 0.5 and float(ps.t["losses"][4]) == 0.5
+    st, _, _ = ps.call(_f32(device, float("nan")), log_rot, grad)
+    ps.assert_bookkeeping(st)
+    assert bool(torch.isnan(ps.t["losses"][5])) and torch.equal(ps.t["best"], best0) and float(ps.t["best_loss"]) == 0.5
+    assert float(ps.t["gnorms"][5]) == 5.0 and torch.equal(grad, _f32(device, [3.0, 4.0, 0.0]))  # no guard
+    assert int(ps.t["it"]) == 6
+    st, _, _ = ps.call(_f32(device, 0.25), log_rot, grad)  # and a better loss still replaces it
+    ps.assert_bookkeeping(st)
+    assert torch.equal(ps.t["best"], log_rot) and float(ps.t["best_loss"]) == 0.25
+
+
+@pytest.mark.parametrize("it", [8, -1, 2 ** 32 + 3])
+def test_pose_step_outside_the_records_writes_nothing(it, device):
+    """t >= niter (also one whose low 32 bits are a valid index) and t < 0: every buffer bitwise as before."""
+    ps = _PoseStep(device, 3, it=it)
+    log_rot, grad = _f32(device, [0.1, 0.2, 0.3]), _f32(device, [3000.0, 4.0, 0.0])
+    loss = _f32(device, 0.01)
+    leaf = [_f32(device, x) for x in (0.5, -1.0, 2.0)]
+    bufs = dict(ps.t, log_rot=log_rot, grad=grad, loss=loss, lr=ps.lr, seed=ps.seed, l0=leaf[0], l1=leaf[1], l2=leaf[2])
+    before = {k: v.clone() for k, v in bufs.items()}
+    st, lr, gr = ps.call(loss, log_rot, grad, leaf=leaf, post=True, adam=True)
+    for k, v in bufs.items():
+        assert torch.equal(v, before[k]), k
+    assert st["it"] == it and np.array_equal(gr, before["grad"].cpu().numpy())  # and so says the restatement
+
+
+def test_pose_step_optional_buffers(device):
+    """acc == NULL with post = 0: neither v nor acc is touched; a NULL leaf_grad[i] adds nothing."""
+    ps = _PoseStep(device, 3)
+    log_rot, grad = _f32(device, [0.1, 0.2, 0.3]), _f32(device, [3.0, 4.0, 0.0])
+    leaf = [_f32(device, x) for x in (0.5, -1.0, 2.0)]
+    v0, acc0 = ps.t["v"].clone(), ps.t["acc"].clone()
+    st, _, _ = ps.call(_f32(device, 0.25), log_rot, grad, leaf=leaf, use_acc=False)
+    assert torch.equal(ps.t["v"], v0) and torch.equal(ps.t["acc"], acc0) and int(ps.t["it"]) == 5
+    assert float(ps.t["losses"][4]) == 0.25 and float(ps.t["gnorms"][4]) == 5.0 and st["acc"] is None
+    st, _, _ = ps.call(_f32(device, 0.3), log_rot, grad, leaf=[leaf[0], None, leaf[2]])
+    ps.assert_bookkeeping(st)
+    assert torch.equal(ps.t["acc"], _f32(device, [1.5, 2.0, 5.0])) and torch.equal(ps.t["v"], v0)
+    st, _, _ = ps.call(_f32(device, 0.3), log_rot, grad, leaf=[None, leaf[1], None], post=True)
+    ps.assert_bookkeeping(st)
+    assert float(ps.t["acc"].abs().max()) == 0.0
+    ema = np.float32(0.9) * v0.cpu().numpy() + np.float32(0.1) * np.float32([1.5, 1.0, 5.0])
+    assert np.array_equal(ps.t["v"].cpu().numpy(), ema)
+
+
+def test_pose_step_adam_64_with_a_guarded_step(device):
+    """Adam over a full row of 64 for 5 steps against torch.optim.Adam (fused, capturable) at
+    test_pose_step_adam_matches_torch_adam's tolerances and against the restatement; the third step's
+    gradient trips the guard, and both references take the replaced gradient the kernel left."""
+    n = 64
+    ps = _PoseStep(device, n, it=0, best_loss=float("inf"))
+    torch.manual_seed(7)
+    ref = torch.randn(1, n, **ps.f32).requires_grad_(True)
+    opt = torch.optim.Adam([ref], lr=torch.tensor(5e-2, **ps.f32), capturable=True, fused=True)
+    mine = ref.detach().clone().reshape(n)
+    for k in range(5):
+        g = torch.randn(n, **ps.f32) * (400.0 if k == 2 else 1.0)  # |g| ~ 3200 > 1000 at k = 2
+        gm = g.clone()
+        st, lr_ref, g_ref = ps.call(_f32(device, 1.0 - 0.1 * k), mine, gm, adam=True)
+        if k == 2:
+            d = pc.guard_draws(12345, 2, n)
+            assert float(ps.t["gnorms"][2]) > 1000.0 and (np.abs(gm.cpu().numpy() - d) <= pc.guard_tol(d)).all()
+        else:
+            assert torch.equal(gm, g)
+        ps.assert_bookkeeping(st)
+        np.testing.assert_allclose(mine.cpu().numpy(), lr_ref, rtol=1e-6, atol=1e-7)
+        np.testing.assert_allclose(ps.t["exp_avg"].cpu().numpy(), st["exp_avg"], rtol=1e-6, atol=1e-8)
+        np.testing.assert_allclose(ps.t["exp_avg_sq"].cpu().numpy(), st["exp_avg_sq"], rtol=1e-6, atol=1e-10)
+        ref.grad = gm.clone().reshape(1, n)
+        opt.step()
+    torch.cuda.synchronize()
+    ost = opt.state[ref]
+    torch.testing.assert_close(mine.reshape(1, n), ref.detach(), rtol=1e-6, atol=1e-7)
+    torch.testing.assert_close(ps.t["exp_avg"].reshape(1, n), ost["exp_avg"], rtol=1e-6, atol=1e-8)
+    torch.testing.assert_close(ps.t["exp_avg_sq"].reshape(1, n), ost["exp_avg_sq"], rtol=1e-6, atol=1e-10)
+    assert float(ps.t["step"]) == float(ost["step"]) == 5.0 and int(ps.t["it"]) == 5
+    assert float(ps.t["best_loss"]) == float(np.float32(1.0 - 0.1 * 4))
