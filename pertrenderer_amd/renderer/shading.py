@@ -25,11 +25,22 @@ F32 = torch.float32
 
 
 def _bc(t, like):
-    """(N,C) / (N,) per-batch parameters broadcast against (N,H,W,K,...) tensors."""
+    """(N,C) / (N,) per-batch parameters broadcast against (N,H,W,K,C) / (N,H,W,K) tensors."""
     t = t.to(like.device)
     if t.dim() == 2:
         return t.reshape((t.shape[0],) + (1,) * (like.dim() - 2) + (t.shape[-1],))
-    return t.reshape((t.shape[0],) + (1,) * (like.dim() - 2))
+    return t.reshape((t.shape[0],) + (1,) * (like.dim() - 1))
+
+
+def _interp(pix_to_face, bary, attr, faces):
+    """interpolate_vertex_attributes for the torch composition: the native kernel on float32 ROCm
+    tensors; as torch ops (PyTorch3D's order, 0 on padded slots) for what that kernel does not take
+    -- CPU tensors and the tests' float64 evaluation of the composition."""
+    if pix_to_face.is_cuda and bary.dtype == F32 and attr.dtype == F32:
+        return interpolate_vertex_attributes(pix_to_face, bary, attr, faces)
+    fa = attr[faces[pix_to_face.clamp(min=0)]]  # (N,H,W,K,3,D)
+    out = (bary[..., 0:1] * fa[..., 0, :] + bary[..., 1:2] * fa[..., 1, :]) + bary[..., 2:3] * fa[..., 2, :]
+    return torch.where((pix_to_face >= 0)[..., None], out, torch.zeros_like(out))
 
 
 def _is_directional(lights):
@@ -61,8 +72,8 @@ def phong_shading_reference(meshes, fragments, lights, cameras, materials, texel
     verts = meshes.verts_packed()
     faces = meshes.faces_packed()
     vnormals = meshes.verts_normals_packed()
-    coords = interpolate_vertex_attributes(fragments.pix_to_face, fragments.bary_coords, verts, faces)
-    normals = interpolate_vertex_attributes(fragments.pix_to_face, fragments.bary_coords, vnormals, faces)
+    coords = _interp(fragments.pix_to_face, fragments.bary_coords, verts, faces)
+    normals = _interp(fragments.pix_to_face, fragments.bary_coords, vnormals, faces)
     N = coords.shape[0]
     expand = lambda t: t.expand(N, -1) if t.shape[0] == 1 else t
     if _is_directional(lights):

@@ -31,7 +31,9 @@ def _interp64(p2f, bary, attr, faces):
 
 
 def _uv_sample64(p2f, bary, tex, dtype=torch.float64):
-    uv = _interp64(p2f, bary, torch.cat([tex.verts_uvs_list()[0]]).to(dtype), tex.faces_uvs_list()[0])
+    fuv = tex.faces_verts_uvs_packed().to(dtype)[p2f.clamp(min=0)]  # (...,3,2): corner UVs of the packed batch's faces
+    uv = ((bary[..., 0:1] * fuv[..., 0, :] + bary[..., 1:2] * fuv[..., 1, :]) + bary[..., 2:3] * fuv[..., 2, :]) \
+        * (p2f >= 0)[..., None]
     N, Ho, Wo, K = p2f.shape
     maps = tex.maps_padded().to(dtype)
     m = torch.flip(maps.permute(0, 3, 1, 2), [2])
@@ -41,6 +43,8 @@ def _uv_sample64(p2f, bary, tex, dtype=torch.float64):
 
 
 def _reference64(mesh, frag, lights, cams, mats, texels, dtype=torch.float64):
+    """The composition in `dtype` on a packed batch: faces and fragments index the packed mesh, the
+    per-image rows ((1 or N, 3) colours, (1 or N,) shininess) broadcast over (N,H,W,K) through sh._bc."""
     d = lambda t: t.to(dtype)
     verts, faces = d(mesh.verts_packed()), mesh.faces_packed()
     # area-weighted vertex normals in float64 (Meshes.verts_normals_packed)
@@ -294,8 +298,9 @@ def test_pixel_block_kernels_match_the_slot_kernels(kind, device, monkeypatch):
     """With the valid-prefix counts attached the shading forward runs as pixel blocks (padded slots
     written as 16-byte stores of the image's colour pattern, live slots enumerated from the counts'
     prefix, pr_shade.hip shade_fwd_pix_kernel); PR_SHADE_PIX=0 forces the per-wave chunk kernel.
-    Colours bit for bit (and the backward, one kernel for both, on them); on a batch of 3 frames
-    whose pixel blocks straddle image boundaries (48^2 pixels = 36 blocks of 64)."""
+    Colours bit for bit (and the backward: the pixel-block kernel against the chunk kernel) on a batch
+    of 3 frames.  48^2 pixels are exactly 36 blocks of 64, so no block here holds two images: blocks
+    that straddle an image boundary, and a tail block, are test_gpu_shading_cases.py's 3 x 5 x 7 frames."""
     from pertrenderer_amd.renderer.rasterizer import Fragments, valid_counts
     mesh, frag, lights, cams, mats, verts, loc, extra = _scene(device, kind)
     assert valid_counts(frag.pix_to_face) is not None
