@@ -17,7 +17,21 @@ indices, since float32 may pick the other of two faces that share the closest po
 Scenes.  Points are drawn in the mesh's bounding box grown by 20 % per side and kept when their
 float64 distance to the mesh is at least 2 % of the box diagonal.  scene() asserts that every
 primitive's best and second-best point differ by >= MIN_GAP in float64 d^2 (faces and edges), so
-the primitive -> point indices of float32 must equal float64's."""
+the primitive -> point indices of float32 must equal float64's.
+
+Known answers.  TRI / REGIONS / DEGENERATE_TRIANGLES / SEGMENT_CASES / ZERO_LENGTH are the hand-built
+table of the closest-point arithmetic: every value is exact in float32 (dyadic numbers of a few
+bits, every divisor a power of two), so equality is asked for, on the CPU and on the device.
+
+Collapsed scenes.  collapsed_scene() copies a face's first vertex position onto its other two
+vertices: that face becomes a point (three ids, one position), its neighbours become (a, a, b) /
+(a, b, b) faces, three of its edges get length 0.  On an (a, b, b) face the segments (a b) and (c a)
+coincide and rounding decides which of them is "nearest first", so the vertex gradient goes to id b
+or to id c: d verts is only well-posed after the rows of bitwise-equal vertex positions have been
+summed (merged_rows, grad_error).  Collinear faces with three distinct positions are left out of
+these scenes: the same closest point is expressed over (a, b), (b, c) or (c, a), so there is no
+unique d verts at all (the float32 restatement's own error reaches 2e-2); the table above covers
+their values."""
 import functools
 
 import torch
@@ -26,10 +40,55 @@ from mesh_loss_cases import brute_edges, case
 
 MESHES = ["triangle", "tetrahedron", "fan3", "hub70", "batch2", "sphere_642"]
 COUNTS = [1, 3, 70, 257]
+# a separate, smaller matrix: clouds that cross the kernel's 512-point tile (one point into the next
+# tile, two tiles and one point); under batch2 the second cloud stays at one point
+TILE_MESHES = ["sphere_642", "hub70", "batch2"]
+TILE_COUNTS = [513, 1025]
 MIN_GAP = 1e-6
 SEEDS = {}  # (mesh, count) -> seed where 0 does not give the gap; found by trying 0, 1, 2, ... on the CPU
 DEGENERATE = 1e-30
 KINDS = ["faces", "edges"]
+
+# ---- the known-answer table
+TRI = [[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]
+# (point, d^2, weights): every value is exact in float32
+REGIONS = {
+    "vertex a": ([-1.0, -1.0, 1.0], 3.0, [1.0, 0.0, 0.0]),
+    "vertex b": ([2.0, -0.5, 0.0], 1.25, [0.0, 1.0, 0.0]),
+    "vertex c": ([-0.5, 2.0, 0.0], 1.25, [0.0, 0.0, 1.0]),
+    "edge ab": ([0.5, -1.0, 0.5], 1.25, [0.5, 0.5, 0.0]),
+    "edge ac": ([-1.0, 0.25, 0.0], 1.0, [0.75, 0.0, 0.25]),
+    "edge bc, in the plane": ([1.0, 1.0, 0.0], 0.5, [0.0, 0.5, 0.5]),
+    "interior": ([0.25, 0.25, 2.0], 4.0, [0.5, 0.25, 0.25]),
+    "on the triangle": ([0.25, 0.5, 0.0], 0.0, [0.25, 0.25, 0.5]),
+    "on a vertex": ([1.0, 0.0, 0.0], 0.0, [0.0, 1.0, 0.0]),
+}
+# (triangle, point, d^2, weights)
+DEGENERATE_TRIANGLES = {
+    # collinear: the segments (a b), (b c), (c a) give 1.25, 1, 1: the first of the equal ones
+    "collinear": ([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [2.0, 0.0, 0.0]], [1.5, 1.0, 0.0], 1.0, [0.0, 0.5, 0.5]),
+    "all equal": ([[1.0, 2.0, 3.0]] * 3, [1.0, 2.0, 5.0], 4.0, [1.0, 0.0, 0.0]),
+}
+# a zero-length segment is its first endpoint: (segment, point, d^2, weights)
+ZERO_LENGTH = ([[1.0, 2.0, 3.0], [1.0, 2.0, 3.0]], [1.0, 0.0, 3.0], 4.0, [1.0, 0.0, 0.0])
+# a segment's interior and its two ends: (point, d^2, weights)
+SEGMENT = [[0.0, 0.0, 0.0], [2.0, 0.0, 0.0]]
+SEGMENT_CASES = [([0.5, 1.0, 0.0], 1.0, [0.75, 0.25, 0.0]), ([-1.0, 0.0, 0.0], 1.0, [1.0, 0.0, 0.0]),
+                 ([3.0, 0.0, 1.0], 2.0, [0.0, 1.0, 0.0])]
+# the point above TRI's interior against TRI's edges: nearest to (a b), at (0.25, 0, 0)
+ABOVE_INTERIOR_TO_EDGES = ([0.25, 0.25, 2.0], 4.0625, [0.75, 0.25, 0.0])
+
+
+def known_edge_cases():
+    """[(label, three vertex positions, point, d^2, weights)] for point_mesh_edge_distance on a mesh of
+    one face (0, 1, 2): its unique edges are (0 1), (0 2), (1 2), the segment under test is (0 1) and
+    the third vertex lies where no other edge is strictly nearer to the point, so edge 0 is chosen
+    (where another edge ends in the same closest vertex it ties exactly and the lowest index wins).
+    The zero-length edge is two ids at one position."""
+    far = [0.0, -8.0, 0.0]
+    out = [("zero-length edge", ZERO_LENGTH[0] + [[1.0, 10.0, 3.0]], *ZERO_LENGTH[1:])]
+    out += [(f"segment case {i}", SEGMENT + [far], p, d2, w) for i, (p, d2, w) in enumerate(SEGMENT_CASES)]
+    return out + [("above the interior", TRI, *ABOVE_INTERIOR_TO_EDGES)]
 
 
 def _dot(a, b):
@@ -187,6 +246,52 @@ def make_scene(name, count, seed):
     return list(verts), list(faces), clouds
 
 
+# ---- collapsed meshes: the faces whose first vertex position is copied onto their other two vertices
+COLLAPSED = {"hub70": (3,), "sphere_642": (5, 700)}
+COLLAPSED_COUNTS = [70, 1025]
+PLANT_RADII = (0.04, 0.05, 0.06)  # of the box diagonal; unequal: equal ones tie exactly on the point-like faces
+
+
+def degenerate_faces(v, f):
+    """Indices of the faces with |n|^2 <= DEGENERATE in float64."""
+    pv = v.double()[f]
+    n = torch.cross(pv[:, 1] - pv[:, 0], pv[:, 2] - pv[:, 0], dim=-1)
+    return (~(_dot(n, n) > DEGENERATE)).nonzero()[:, 0]
+
+
+def make_collapsed_scene(name, count, seed):
+    verts, faces = case(name)
+    v, f = verts[0].detach().clone(), faces[0]
+    centre = v.mean(0)
+    diag = (v.max(0).values - v.min(0).values).norm()
+    planted = []
+    for i in COLLAPSED[name]:
+        a, b, c = f[i].tolist()
+        v[b] = v[c] = v[a]
+        out = (v[a] - centre) / (v[a] - centre).norm()  # outwards: the meshes are centred at their mean
+        planted += [v[a] + r * diag * out for r in PLANT_RADII]
+    g = torch.Generator().manual_seed(seed)
+    pts = torch.cat([_draw(v, f, count - len(planted), g), torch.stack(planted)])
+    return [v], [f], [pts.contiguous()]
+
+
+def merged_rows(grad, verts):
+    """A packed (V,3) vertex gradient with the rows of bitwise-equal vertex positions (of one mesh)
+    summed, in float64 on the CPU: what d verts is compared as on a collapsed mesh."""
+    mesh = torch.cat([torch.full((v.shape[0], 1), float(i), dtype=torch.float64) for i, v in enumerate(verts)])
+    key = torch.cat([torch.cat(list(verts)).double().cpu(), mesh], 1)
+    uniq, inverse = torch.unique(key, dim=0, return_inverse=True)
+    return torch.zeros((uniq.shape[0], 3), dtype=torch.float64).index_add_(0, inverse, grad.detach().double().cpu())
+
+
+def grad_error(got, want, key, merge=None):
+    """max-abs over max-abs; with merge = the verts list a vertex gradient is compared through merged_rows."""
+    from mesh_loss_cases import rel_err
+    if merge is not None and key.endswith("verts"):
+        got, want = merged_rows(got, merge), merged_rows(want, merge)
+    return rel_err(got, want)
+
+
 def min_gap(verts, faces, clouds, skip=()):
     """The smallest best-to-second-best gap in float64 d^2 over every primitive (faces and edges) of
     every batch element with at least two points; the packed-to-local point columns in `skip` are left out."""
@@ -201,39 +306,72 @@ def min_gap(verts, faces, clouds, skip=()):
     return worst
 
 
-@functools.lru_cache(maxsize=None)
-def scene(name, count):
+def scene(name, count, collapsed=False):
     """(verts list, faces list, clouds list), float32 on the CPU; the gap rule is asserted."""
+    return collapsed_scene(name, count) if collapsed else _clean_scene(name, count)
+
+
+@functools.lru_cache(maxsize=None)
+def _clean_scene(name, count):
     s = make_scene(name, count, SEEDS.get((name, count), 0))
     assert min_gap(*s) >= MIN_GAP, (name, count, min_gap(*s))
     return s
 
 
+@functools.lru_cache(maxsize=None)
+def collapsed_scene(name, count):
+    """scene() on the collapsed mesh of `name`, with three points planted outwards of every collapsed
+    vertex.  Asserted: the degenerate primitives are there, the gap rule, and on hub70 that a
+    degenerate face is some point's float64 choice (degenerate_choices)."""
+    s = make_collapsed_scene(name, count, SEEDS.get((name, count, "collapsed"), 0))
+    v, f = s[0][0], s[1][0]
+    flat = degenerate_faces(v, f)
+    assert set(COLLAPSED[name]) <= set(flat.tolist()) and len(flat) >= 3 * len(COLLAPSED[name])
+    for i in COLLAPSED[name]:
+        assert torch.equal(v[f[i]], v[f[i, :1]].expand(3, 3)), "three ids, one position"
+    e = torch.tensor(brute_edges(f))
+    assert (v[e[:, 0]] == v[e[:, 1]]).all(dim=1).sum() == 3 * len(COLLAPSED[name]), "zero-length edges"
+    assert min_gap(*s) >= MIN_GAP, (name, count, min_gap(*s))
+    assert name != "hub70" or degenerate_choices(*s) > 0, (name, count)
+    return s
+
+
+def degenerate_choices(verts, faces, clouds):
+    """How many points have a degenerate face as their float64 choice (the first minimum)."""
+    chosen = dense_d2(verts, faces, clouds, "faces")[0].argmin(dim=1)
+    return torch.isin(chosen, degenerate_faces(verts[0], faces[0])).sum().item()
+
+
 # ---- planted exact ties: face TIE_FACE of sphere_642 copied into the middle and to the end of the
 # face list (with the faces cut into three ranges, or into eleven, the copies lie in the first, a
 # middle and the last range); point TIE_POINT sits above that face's centroid, so the copies are its
-# nearest faces at exactly equal d^2; point 1 is duplicated as the last point.
-TIE_FACE, TIE_POINT, TIE_COUNT = 5, 2, 70
+# nearest faces at exactly equal d^2; the first point (after point 0, not TIE_POINT) that is the
+# nearest point of some face and of some edge is duplicated as the last point: point 1 with TIE_COUNT
+# points.  With TIE_COUNT_FAR points the two copies are two 512-point tiles apart: in the first and
+# the third tile of one range, or in the first and the last of two or three ranges.
+TIE_FACE, TIE_POINT, TIE_COUNT, TIE_COUNT_FAR = 5, 2, 70, 1025
 
 
 @functools.lru_cache(maxsize=None)
-def tie_scene():
+def tie_scene(count=TIE_COUNT):
     """(verts list, faces list, clouds list, copies (face indices, ascending), duplicates (point indices))."""
     verts, faces = case("sphere_642")
     v, f = verts[0].detach(), faces[0]
     mid = f.shape[0] // 2
     f = torch.cat([f[:mid], f[TIE_FACE:TIE_FACE + 1], f[mid:], f[TIE_FACE:TIE_FACE + 1]])
     copies = (TIE_FACE, mid, f.shape[0] - 1)
-    pts = _draw(v, f, TIE_COUNT, torch.Generator().manual_seed(0)).clone()
+    pts = _draw(v, f, count, torch.Generator().manual_seed(SEEDS.get(("tie", count), 0))).clone()
     a, b, c = (v[i] for i in f[TIE_FACE])
     n = torch.cross(b - a, c - a, dim=0)
     n = n / n.norm()
     centre = (a + b + c) / 3
     n = n if (n * centre).sum() > 0 else -n  # outwards: the sphere is centred at the origin
     pts[TIE_POINT] = centre + 0.05 * (v.max(0).values - v.min(0).values).norm() * n
-    pts[-1] = pts[1]
-    dup = (1, TIE_COUNT - 1)
-    assert min_gap([v], [f], [pts], skip=(dup[1],)) >= MIN_GAP
+    nearest = [d[:-1].argmin(dim=0) for d in (dense_d2([v], [f], [pts], k)[0] for k in KINDS)]
+    first = min(j for j in range(1, count - 1) if j != TIE_POINT and all((n == j).any() for n in nearest))
+    pts[-1] = pts[first]
+    dup = (first, count - 1)
+    assert min_gap([v], [f], [pts], skip=(dup[1],)) >= MIN_GAP, (count, min_gap([v], [f], [pts], skip=(dup[1],)))
     return [v], [f], [pts], copies, dup
 
 
@@ -242,10 +380,14 @@ def random_cotangent(P, M, seed=7):
     return torch.randn(P, generator=g), torch.randn(M, generator=g)
 
 
-@functools.lru_cache(maxsize=None)
-def references(name, count, kind):
+def references(name, count, kind, collapsed=False):
     """(float64 restatement with the loss's and the raw outputs' gradients, the cotangent), once per case."""
-    verts, faces, clouds = scene(name, count)
+    return _references(name, count, kind, bool(collapsed))
+
+
+@functools.lru_cache(maxsize=None)
+def _references(name, count, kind, collapsed):
+    verts, faces, clouds = scene(name, count, collapsed)
     M = sum(p.shape[0] for p in prims_of(verts, faces, kind))
     cot = random_cotangent(sum(c.shape[0] for c in clouds), M)
     return reference(verts, faces, clouds, kind, cot=cot), cot
@@ -255,14 +397,14 @@ GRAD_KEYS = ("grad_points", "grad_verts", "raw_grad_points", "raw_grad_verts")
 MAX_RESTATEMENT_ERROR = 2e-5  # of the float32 restatement's gradients; keeps the 4x rule from loosening
 
 
-def float32_errors(name, count, kind, idx):
+def float32_errors(name, count, kind, idx, collapsed=False):
     """{key: max-abs over max-abs error} of the float32 restatement against float64, both evaluated at
-    the packed indices idx = (idx_p, idx_m); asserted to stay below MAX_RESTATEMENT_ERROR."""
-    from mesh_loss_cases import rel_err
-    verts, faces, clouds = scene(name, count)
-    _, cot = references(name, count, kind)
+    the packed indices idx = (idx_p, idx_m); asserted to stay below MAX_RESTATEMENT_ERROR.  On a
+    collapsed scene the vertex gradients are compared through merged_rows."""
+    verts, faces, clouds = scene(name, count, collapsed)
+    _, cot = references(name, count, kind, collapsed)
     r64 = reference(verts, faces, clouds, kind, idx=idx, cot=cot)
     r32 = reference(verts, faces, clouds, kind, dtype=torch.float32, idx=idx, cot=cot)
-    err = {k: rel_err(r32[k], r64[k]) for k in GRAD_KEYS}
+    err = {k: grad_error(r32[k], r64[k], k, verts if collapsed else None) for k in GRAD_KEYS}
     assert max(err.values()) <= MAX_RESTATEMENT_ERROR, (name, count, kind, err)
     return r64, err

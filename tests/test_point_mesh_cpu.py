@@ -11,26 +11,10 @@ from mesh_loss_cases import brute_edges, case, packed, rel_err
 from pertrenderer_amd import renderer
 from pertrenderer_amd.renderer import Meshes, Pointclouds
 from pertrenderer_amd.renderer import loss as L
+# the known-answer table, shared with the device tests (test_gpu_point_mesh.py)
+from point_mesh_cases import DEGENERATE_TRIANGLES as DEGENERATE, REGIONS, SEGMENT, SEGMENT_CASES, TRI, ZERO_LENGTH
 
 FN = {"faces": L.point_mesh_face_distance, "edges": L.point_mesh_edge_distance}
-TRI = [[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [0.0, 1.0, 0.0]]
-# (point, d^2, weights): every value is exact in float32
-REGIONS = {
-    "vertex a": ([-1.0, -1.0, 1.0], 3.0, [1.0, 0.0, 0.0]),
-    "vertex b": ([2.0, -0.5, 0.0], 1.25, [0.0, 1.0, 0.0]),
-    "vertex c": ([-0.5, 2.0, 0.0], 1.25, [0.0, 0.0, 1.0]),
-    "edge ab": ([0.5, -1.0, 0.5], 1.25, [0.5, 0.5, 0.0]),
-    "edge ac": ([-1.0, 0.25, 0.0], 1.0, [0.75, 0.0, 0.25]),
-    "edge bc, in the plane": ([1.0, 1.0, 0.0], 0.5, [0.0, 0.5, 0.5]),
-    "interior": ([0.25, 0.25, 2.0], 4.0, [0.5, 0.25, 0.25]),
-    "on the triangle": ([0.25, 0.5, 0.0], 0.0, [0.25, 0.25, 0.5]),
-    "on a vertex": ([1.0, 0.0, 0.0], 0.0, [0.0, 1.0, 0.0]),
-}
-DEGENERATE = {
-    # collinear: the segments (a b), (b c), (c a) give 1.25, 1, 1: the first of the equal ones
-    "collinear": ([[0.0, 0.0, 0.0], [1.0, 0.0, 0.0], [2.0, 0.0, 0.0]], [1.5, 1.0, 0.0], 1.0, [0.0, 0.5, 0.5]),
-    "all equal": ([[1.0, 2.0, 3.0]] * 3, [1.0, 2.0, 5.0], 4.0, [1.0, 0.0, 0.0]),
-}
 
 
 def _closest_fns():
@@ -50,13 +34,12 @@ def test_known_answers_of_the_voronoi_regions(which, dtype):
         d, got = fn(torch.tensor([p], dtype=dtype), torch.tensor([t], dtype=dtype))
         assert d.item() == d2 and torch.equal(got[0], torch.tensor(w, dtype=dtype)), (name, d.item(), got)
     # a zero-length edge is its endpoint
-    seg = torch.tensor([[[1.0, 2.0, 3.0], [1.0, 2.0, 3.0]]], dtype=dtype)
-    d, got = fn(torch.tensor([[1.0, 0.0, 3.0]], dtype=dtype), seg)
-    assert d.item() == 4.0 and torch.equal(got[0], torch.tensor([1.0, 0.0, 0.0], dtype=dtype))
+    s, p, d2, w = ZERO_LENGTH
+    d, got = fn(torch.tensor([p], dtype=dtype), torch.tensor([s], dtype=dtype))
+    assert d.item() == d2 == 4.0 and torch.equal(got[0], torch.tensor(w, dtype=dtype)) and w == [1.0, 0.0, 0.0]
     # a segment's interior and its two ends
-    seg = torch.tensor([[[0.0, 0.0, 0.0], [2.0, 0.0, 0.0]]], dtype=dtype)
-    for p, d2, w in (([0.5, 1.0, 0.0], 1.0, [0.75, 0.25, 0.0]), ([-1.0, 0.0, 0.0], 1.0, [1.0, 0.0, 0.0]),
-                     ([3.0, 0.0, 1.0], 2.0, [0.0, 1.0, 0.0])):
+    seg = torch.tensor([SEGMENT], dtype=dtype)
+    for p, d2, w in SEGMENT_CASES:
         d, got = fn(torch.tensor([p], dtype=dtype), seg)
         assert d.item() == d2 and torch.equal(got[0], torch.tensor(w, dtype=dtype)), (p, d.item(), got)
 
@@ -71,8 +54,66 @@ def test_known_answers_through_the_public_functions():
     loss = L.point_mesh_face_distance(mesh, Pointclouds([pts]))
     assert loss.dim() == 0 and loss.item() == pytest.approx(want.mean().item(), rel=1e-6)
     # the edges of the triangle: the point above the interior is nearest to (a b), at (0.25, 0, 0)
-    dist_p = L._point_mesh_nn(mesh, Pointclouds([pts[6:7]]), "edges")[0]
-    assert dist_p.item() == 4.0625
+    p, d2, w = C.ABOVE_INTERIOR_TO_EDGES
+    assert p == REGIONS["interior"][0] and d2 == 4.0625
+    dist_p, _, idx_p, _, w_p = L._point_mesh_nn(mesh, Pointclouds([torch.tensor([p])]), "edges")[:5]
+    assert dist_p.item() == d2 and idx_p.item() == 0 and torch.equal(w_p[0], torch.tensor(w))
+
+
+def test_known_answers_of_the_edges_through_the_public_functions():
+    """The hand-built edge meshes of the device tests: the composition gives the table's values at edge 0."""
+    for label, tri, p, d2, w in C.known_edge_cases():
+        mesh = Meshes([torch.tensor(tri)], [torch.tensor([[0, 1, 2]])])
+        dist_p, dist_m, idx_p, idx_m, w_p, w_m = L._point_mesh_nn(mesh, Pointclouds([torch.tensor([p])]), "edges")[:6]
+        assert dist_p.item() == d2 and idx_p.item() == 0 and torch.equal(w_p[0], torch.tensor(w)), (label, dist_p, w_p)
+        assert dist_m[0].item() == d2 and (idx_m == 0).all() and torch.equal(w_m[0], torch.tensor(w)), (label, dist_m, w_m)
+
+
+# every scene the device tests add: (mesh, count, collapsed)
+DEVICE_SCENES = ([(n, c, False) for n in C.TILE_MESHES for c in C.TILE_COUNTS]
+                 + [(n, c, True) for n in C.COLLAPSED for c in C.COLLAPSED_COUNTS])
+
+
+@pytest.mark.parametrize("name,count,collapsed", DEVICE_SCENES)
+def test_conditions_of_the_device_scenes(name, count, collapsed):
+    """What the device tests rely on, checked without a device: the gap rule (asserted by the
+    builder, stated again here), the float32 restatement's gradient error at float64's indices
+    within MAX_RESTATEMENT_ERROR (on a collapsed mesh with the d verts rows of equal positions
+    summed), and on the collapsed hub70 a degenerate face among the points' float64 choices."""
+    verts, faces, clouds = C.scene(name, count, collapsed)
+    assert [c.shape[0] for c in clouds] == C.lengths_of(name, count)
+    assert C.min_gap(verts, faces, clouds) >= C.MIN_GAP
+    for kind in C.KINDS:
+        want, _ = C.references(name, count, kind, collapsed)
+        _, err = C.float32_errors(name, count, kind, (want["idx_p"], want["idx_m"]), collapsed)
+        assert max(err.values()) <= C.MAX_RESTATEMENT_ERROR, (kind, err)
+        print(f"{name} {count} collapsed={collapsed} {kind}: restatement(fp32) "
+              + ", ".join(f"{k} {e:.2e}" for k, e in err.items()))
+    if collapsed:
+        assert len(C.degenerate_faces(verts[0], faces[0])) >= 3 * len(C.COLLAPSED[name])
+        if name == "hub70":
+            assert C.degenerate_choices(verts, faces, clouds) > 0
+
+
+def test_merged_rows_sums_equal_positions_per_mesh():
+    v = torch.tensor([[1.0, 2.0, 3.0], [0.0, 0.0, 0.0], [1.0, 2.0, 3.0]])
+    g = torch.tensor([[1.0, 0.0, 0.0], [0.0, 5.0, 0.0], [0.0, 0.0, 2.0]])
+    got = C.merged_rows(g, [v])
+    assert got.shape == (2, 3) and sorted(got.tolist()) == [[0.0, 5.0, 0.0], [1.0, 0.0, 2.0]]
+    # equal positions of different meshes stay apart; a swap between coincident ids of one mesh is not seen
+    assert C.merged_rows(torch.cat([g, g]), [v, v]).shape == (4, 3)
+    assert C.grad_error(g[[2, 1, 0]], g, "grad_verts", [v]) == 0.0 and C.grad_error(g[[2, 1, 0]], g, "grad_verts") > 0.0
+
+
+def test_far_tie_scene_splits_the_duplicates_over_tiles_and_ranges():
+    verts, faces, clouds, copies, dup = C.tie_scene(C.TIE_COUNT_FAR)
+    assert C.tie_scene()[4] == (1, C.TIE_COUNT - 1)  # the scene of the 70-point tests is what it was
+    assert clouds[0].shape[0] == 1025 and dup[1] == 1024 and torch.equal(clouds[0][dup[0]], clouds[0][1024])
+    assert dup[1] - dup[0] > 512 and dup[0] // 512 == 0 and dup[1] // 512 == 2  # one range: the first and the third tile
+    assert all(dup[0] // -(-1025 // s) == 0 and dup[1] // -(-1025 // s) == s - 1 for s in (2, 3))  # first and last range
+    for kind in C.KINDS:
+        want = C.reference(verts, faces, clouds, kind)
+        assert (want["idx_m"] == dup[0]).any() and not (want["idx_m"] == dup[1]).any()
 
 
 def _grads(out, c, v):
